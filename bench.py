@@ -19,6 +19,11 @@ the ranks; each rank stages and runs only its own workers' reads (no steady-stat
 model at start-up) => weak scaling.  --job-workers T: range sharding instead (every rank owns all T workers and
 generates a range of each batch; one all-gather of per-stream sample counts per batch).
 
+A plain run sets up, warms up, times the --steps steps and prints the line; --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs).  Everything else -- the CPU baseline and the parity check against the oracle, the streaming,
+small-batch and end-to-end legs, kernel_ms over every batch, the store and LDS-order probes, the per-rank parity check (N > 1)
+and the live PMC passes -- runs with --full only.
+
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (k_samples_lean) against HBM: achieved =
 algorithmic bytes (2*N_samples + N_bases + 24*N_reads per launch) / its average launch duration measured
 with hipEvents on the library's stream; `step_frac` is the same bytes over the whole step, `step_traffic(_frac)` all the HBM bytes of a
@@ -358,7 +363,7 @@ def live_traffic(args, limit_s=180.0):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if exe is None or under_profiler():
         return None
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--pipeline-seconds", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--pipeline-seconds", "0",
              "--e2e-seconds", "0", "--small-batch-seconds", "0", "--every-batch-launches", "0", "--live-traffic", "off",
              "--workload", args.workload, "--rlen", str(args.rlen), "--mode", args.mode]
     if args.batch_reads is not None:
@@ -790,6 +795,37 @@ def e2e_legs(gen, prof, flags, sample_batch, reads_per_batch, seconds, kinds=("p
     return out
 
 
+DUMP_BYTES = 64_000_000
+DUMP_SEED = 20240611
+
+
+def dump_outputs(b, out_dir, device):
+    """--dump-outputs: what a caller of the timed path receives for the waited-for batch `b` (the last timed step), as .npy files in
+    `out_dir`: per read, the length of its signal, its slow5 offset and median_before (float64, every read); the batch's totals
+    (float64: reads, samples, events, bases); and the int16 samples of a fixed, seeded sample of its reads as float32 -- whole reads in
+    a seeded order while the files stay under DUMP_BYTES -- with the indices of those reads (float64, ascending).  The samples are
+    gathered in HBM (a step holds gigabytes of them)."""
+    import torch
+    n = b.n_reads
+    sig_len = np.diff(b.sig_off)
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    room = DUMP_BYTES - 8 * (4 * n + 4) - 6 * 4096                      # (the float64 arrays, at most n indices, the .npy headers)
+    pick = np.sort(order[:int(np.searchsorted(4 * np.cumsum(sig_len[order]), room, side="right"))])
+    signal = np.zeros(0, np.float32)
+    if b.n_samples > 0 and len(pick):
+        class _Signal:                                                  # sqg_result_t.d_signal, dressed for torch.as_tensor (zero-copy)
+            __cuda_array_interface__ = {"shape": (int(b.n_samples),), "typestr": "<i2", "data": (b.res.d_signal, False), "version": 2}
+        d_sig = torch.as_tensor(_Signal(), device=device)
+        signal = torch.cat([d_sig[int(b.sig_off[i]):int(b.sig_off[i + 1])] for i in pick]).float().cpu().numpy()
+    out = {"sig_len": sig_len.astype(np.float64), "offset": np.asarray(b.offset, np.float64),
+           "median_before": np.asarray(b.median_before, np.float64),
+           "totals": np.array([n, b.n_samples, b.n_events, b.n_bases], np.float64),
+           "signal_read_index": pick.astype(np.float64), "signal": signal}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -868,7 +904,21 @@ def main():
     ap.add_argument("--digest", type=int, default=0,
                     help="D > 0 (tests): fetch every timed batch's signal and report, per batch, the sums of the reads' xxh64 digests "
                          "over D equal parts of the job's batch (N ranks report N*D/N parts each)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU baseline and parity check, the streaming, small-batch and end-to-end legs, "
+                         "kernel_ms over every batch, the store and LDS-order probes, the per-rank parity check and the live PMC passes "
+                         "(their options -- --cpu-seconds, --pipeline-seconds, --e2e-seconds, ... -- apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32/float64, under 64 MB (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_store_probe = args.no_rank_parity = True
+        args.pipeline_seconds = args.e2e_seconds = args.small_batch_seconds = 0
+        args.every_batch_launches = 0
+        args.live_traffic = "off"
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs at least one timed step")
     if args.lib:
         os.environ["SQG_LIB"] = os.path.abspath(args.lib)
     elif os.environ.get("SQG_LIB"):
@@ -1085,6 +1135,8 @@ def main():
                     acc = (acc + xxhash.xxh64(sig[b.sig_off[i]:b.sig_off[i + 1]].tobytes()).intdigest()) & 0xFFFFFFFFFFFFFFFF
                 parts.append(acc)
             digests.append(parts)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(timed[-1], args.dump_outputs, dev)       # (before any other leg runs on the context: its slabs still hold the step)
 
     on_gpu = not use_dist or args.backend == "nccl"
     tot = torch.tensor([float(samples), float(reads), dt], dtype=torch.float64, device="cuda" if on_gpu else "cpu")
@@ -1197,7 +1249,7 @@ def main():
     # which stream hand-out the timed steps used: the one that relies on lane-ordered LDS atomics (probed at create time, re-checked on a
     # sample of every slice of every batch) or -- a device that fails the probe, or --order-free -- the claim protocol (1.3 ms per step slower)
     lds_order = None
-    if rank == 0:
+    if rank == 0 and args.full:
         bad_, used_ = gen.probe_lds_order(256, 4)
         lds_order = {"in_use": used_, "probe_mismatches": bad_}
     store_peak_GBps = None

@@ -28,3 +28,7 @@ REFVEC_CASES = [
     ("r9_meth_tk4", "nCoV-2019.reference.fasta -x dna-r9-prom -n 8 --seed 11 -r 1200 -t 4 -K 4 --meth-freq mfreq_dense.tsv"),
     ("r10_meth_dense", "nCoV-2019.reference.fasta -x dna-r10-prom -n 3 --seed 2 -r 1200 -t1 --meth-freq mfreq_dense.tsv"),
 ]
+
+# the randomised commands of test_oracle_vs_ref.test_oracle_matches_live_reference: vectors tests/golden/refvec/live_seed<seed>.npz
+LIVE_SEEDS = [3, 12345]
+LIVE_CMD = "nCoV-2019.reference.fasta -x dna-r10-prom -n 6 --seed {seed} -r 800 -t 3 -K 3 --amp-noise 1.7 --dwell-std 6"

@@ -40,7 +40,7 @@ def _bench(*args):
 ], ids=lambda v: v if isinstance(v, str) else None)
 def test_two_ranks_equal_one(name, single, dual):
     one = _bench("--gpus", 1, *single)
-    two = _bench("--gpus", 2, "--backend", "gloo", *dual)
+    two = _bench("--gpus", 2, "--backend", "gloo", "--full", *dual)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["steps"] == 2 and len(two["digest"]) == 2
     assert one["digest"] == two["digest"], (one["digest"], two["digest"])
@@ -70,7 +70,7 @@ def test_eight_ranks_equal_one(name, single, eight):
     """world size 8 -- eight contexts, eight staging pools, shard.worker_range(r, 8, 8), the 8-way exchange -- sharing the box's GPU
     (--backend gloo): read for read the single-rank run of the same job"""
     one = _bench("--gpus", 1, *single)
-    many = _bench("--gpus", 8, "--backend", "gloo", *eight)
+    many = _bench("--gpus", 8, "--backend", "gloo", "--full", *eight)
     assert many["n_gpus"] == 8 and many["ranks"]["world_size"] == 8 and len(many["digest"]) == 2 and len(many["digest"][0]) == 8
     assert one["digest"] == many["digest"], (one["digest"], many["digest"])
     assert many["reads_per_s"] * many["ms_per_step"] * 1e-3 * many["steps"] == pytest.approx(2 * 2048, rel=1e-6)
@@ -83,7 +83,7 @@ def test_eight_ranks_equal_one(name, single, eight):
 def test_eight_ranks_stream_on_the_box_cpu_quota():
     """the streaming leg with eight ranks on the box's CPU quota (16 CPUs on the pool's boxes): every rank sizes its staging helpers
     from its share of the quota (bench.py: sqg_set_stage_threads), reports its host time per batch, and the leg completes on every rank"""
-    d = _bench("--gpus", 8, "--backend", "gloo", "--genome-mb", 24, "--batch-reads", 512, "--workers-per-gpu", 1, "--pipeline-seconds", 0.5)
+    d = _bench("--gpus", 8, "--backend", "gloo", "--full", "--genome-mb", 24, "--batch-reads", 512, "--workers-per-gpu", 1, "--pipeline-seconds", 0.5)
     pl = d["pipeline"]
     assert d["n_gpus"] == 8 and pl["value"] > 0 and pl["batches_per_gpu"] >= 9
     assert 0 < pl["host_stage_ms_per_batch_min"] <= pl["host_stage_ms_per_batch"] <= pl["host_stage_ms_per_batch_max"]
@@ -133,12 +133,12 @@ def test_gpus_flag_without_enough_devices_fails_loudly():
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract():
-    """the one JSON line of the driver's command (small genome and batches, short CPU legs): every field the contract names, the
+    """the one JSON line of the full run (--full; small genome and batches, short CPU legs): every field the contract names, the
     roofline and cpu_baseline objects, the parity check of the timed regime"""
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--genome-mb", "24",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--genome-mb", "24",
                         "--batch-reads", "1024", "--cpu-seconds", "1", "--pipeline-seconds", "0.5", "--e2e-seconds", "0.3", "--small-batch-seconds", "0.3"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -313,7 +313,7 @@ def test_bench_other_workloads(workload, profile, regime):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--steps", "3", "--warmup", "1",
                         "--batch-reads", "2048", "--cpu-seconds", "1", "--pipeline-seconds", "0.2", "--e2e-seconds", "0", "--small-batch-seconds", "0"], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -328,10 +328,42 @@ def test_two_ranks_run_the_streaming_leg_and_report_their_clocks():
     """N > 1 without --digest: the timed steps, then the streaming leg on every rank (the same number of batches everywhere: range
     sharding has a collective per batch), reductions over the ranks, `ranks` and `pipeline` in rank 0's line"""
     for extra in (["--workers-per-gpu", 1], ["--job-workers", 1]):
-        d = _bench("--gpus", 2, "--backend", "gloo", "--genome-mb", 24, "--batch-reads", 512, "--pipeline-seconds", 0.3, *extra)
+        d = _bench("--gpus", 2, "--backend", "gloo", "--full", "--genome-mb", 24, "--batch-reads", 512, "--pipeline-seconds", 0.3, *extra)
         assert d["n_gpus"] == 2 and d["ranks"]["world_size"] == 2 and d["ranks"]["backend"] == "gloo"
         assert d["ranks"]["ms_per_step_min"] <= d["ranks"]["ms_per_step_max"] == pytest.approx(d["ms_per_step"], rel=1e-9)
         pl = d["pipeline"]
         assert pl["value"] > 0 and pl["batches_per_gpu"] >= 9 and pl["reads_per_s"] > 0
         # both ranks' samples are in the whole-job numbers
         assert d["value"] * d["ms_per_step"] * 1e-3 > d["samples_per_step_per_gpu"]
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full: the headline and none of the other legs.  --dump-outputs: the last timed step's results, the same files from a
+    run of the same job, and the dumped signals are those of that step's reads (their xxh64 digests, --digest with one read per part)"""
+    import xxhash
+    import numpy as np
+    args = ["--gpus", 1, "--genome-mb", 24, "--workers-per-gpu", 1, "--batch-reads", 1024, "--place-batches", 0]
+    d = _bench(*args, "--dump-outputs", tmp_path / "a")
+    assert d["metric"] == "simulated raw samples/sec" and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and isinstance(d["dtype"], str)
+    for leg in ("cpu_baseline", "pipeline", "e2e", "small_batch", "kernel_ms_every_batch"):
+        assert d[leg] is None, leg
+    assert "parity_check" not in d and d["config"]["lds_ordered_hand_out"] is None and d["roofline"].get("traffic_source") != "live"
+    dg = _bench(*args, "--digest", 1024, "--dump-outputs", tmp_path / "b")          # (--digest runs no placement batches either)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "signal.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6
+    for n in names:
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes(), n
+    out = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    n_reads, n_samples = out["totals"][:2]
+    assert n_reads == 1024 and out["sig_len"].sum() == n_samples and len(out["offset"]) == len(out["median_before"]) == 1024
+    idx = out["signal_read_index"].astype(np.int64)
+    assert len(idx) > 0 and len(out["signal"]) == out["sig_len"][idx].sum()
+    at = 0
+    for i in idx:
+        n = int(out["sig_len"][i])
+        assert xxhash.xxh64(out["signal"][at:at + n].astype(np.int16).tobytes()).intdigest() == dg["digest"][-1][i], i
+        at += n

@@ -2,8 +2,8 @@
 
 The vectors in tests/golden/refvec/*.npz were produced in the build container by
 oracle/_ref/ref_harness (the reference's translation units compiled where they lie, driven by
-oracle/ref_harness.c) -- see tools/make_refvec.py.  When the harness binary and /root/reference
-are present the comparison is additionally made live, including a randomized case.
+oracle/ref_harness.c) -- see tools/make_refvec.py.  Where that harness was built (oracle/_ref, made by
+build() where the upstream tree is mounted) the randomised cases are additionally compared with a live run of it.
 """
 import os
 import sys
@@ -14,7 +14,7 @@ import pytest
 
 import orc
 import simrun
-from refvec_cases import REFVEC_CASES
+from refvec_cases import LIVE_CMD, LIVE_SEEDS, REFVEC_CASES
 from squigulator_amd import model, options
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,17 +58,22 @@ def test_oracle_thread_count_invariance():
     orac.close()
 
 
-@pytest.mark.skipif(not (os.path.exists(HARNESS) and os.path.isdir("/root/reference")),
-                    reason="compiled reference harness only exists in the build container")
-@pytest.mark.parametrize("seed", [3, 12345])
+@pytest.mark.parametrize("seed", LIVE_SEEDS)
 def test_oracle_matches_live_reference(seed):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import make_refvec
-    cmd = f"nCoV-2019.reference.fasta -x dna-r10-prom -n 6 --seed {seed} -r 800 -t 3 -K 3 --amp-noise 1.7 --dwell-std 6"
-    with tempfile.TemporaryDirectory() as tmp:
-        make_refvec._model_files.clear()
-        ref_reads, k = make_refvec.run_harness(cmd, tmp)
-    v = make_refvec.pack(ref_reads)
+    """randomised amplitude and dwell options: the reference's vectors of the command (tests/golden/refvec/live_seed<seed>.npz), and a
+    live run of the compiled reference wherever the harness exists"""
+    cmd = LIVE_CMD.format(seed=seed)
+    v = np.load(os.path.join(VEC, f"live_seed{seed}.npz"))
+    assert str(v["cmd"]) == cmd, "fixture was generated from a different command line; rerun tools/make_refvec.py"
     o, k2, names, lengths, reads, orac = simrun.run_oracle(cmd)
+    assert k2 == int(v["k"])
     _check(reads, v)
+    if os.path.exists(HARNESS):
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import make_refvec
+        with tempfile.TemporaryDirectory() as tmp:
+            make_refvec._model_files.clear()
+            ref_reads, k = make_refvec.run_harness(cmd, tmp)
+        assert k == k2
+        _check(reads, make_refvec.pack(ref_reads))
     orac.close()

@@ -4,6 +4,7 @@ CPU: the oracle restatement against bytes produced by the reference's own slow5l
 tools/make_svbvec.py through oracle/_ref/ref_harness), and the round trip.  GPU: the device coder against the
 oracle on simulated batches, plus the decode round trip at full size."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -34,27 +35,20 @@ def test_oracle_svb_zd_equals_slow5lib_bytes():
 
 
 def test_live_against_slow5lib_when_reference_is_mounted(tmp_path):
-    """Randomised arrays through the compiled reference (only where /root/reference exists)."""
-    import struct
-    import subprocess
-    harness = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "ref_harness")
-    if not (os.path.isdir("/root/reference") and os.path.exists(harness)):
-        pytest.skip("compiled reference not available")
-    rng = np.random.default_rng(7)
-    arrs = [rng.integers(-32768, 32768, int(n)).astype(np.int16) for n in rng.integers(0, 5000, 20)]
-    arrs += [(rng.integers(200, 900) + 50 * rng.standard_normal(int(n))).astype(np.int16) for n in rng.integers(1, 50000, 10)]
-    fin, fout, cfg = (str(tmp_path / x) for x in ("in.bin", "out.bin", "cfg.txt"))
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<i", len(arrs)))
-        for a in arrs:
-            f.write(struct.pack("<q", len(a)) + a.tobytes())
-    open(cfg, "w").write(f"svb_in={fin}\nsvb_out={fout}\n")
-    subprocess.check_call([harness, cfg])
-    buf = open(fout, "rb").read()
-    p = 0
-    for a in arrs:
-        (nb,) = struct.unpack_from("<q", buf, p); p += 8
-        np.testing.assert_array_equal(orc.svb_zd(a), np.frombuffer(buf, np.uint8, nb, p)); p += nb
+    """Randomised arrays: the reference's encodings by length and SHA-256 (tests/golden/svb/svb_live.npz, tools/make_svbvec.py), and
+    byte for byte from a live run of the compiled reference wherever its harness exists."""
+    import hashlib
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
+    import make_svbvec
+    arrs = make_svbvec.live_cases()
+    want = np.load(os.path.join(os.path.dirname(__file__), "golden", "svb", "svb_live.npz"))
+    assert len(want["enc_lens"]) == len(arrs)
+    for a, nb, h in zip(arrs, want["enc_lens"], want["enc_sha256"]):
+        got = orc.svb_zd(a)
+        assert len(got) == nb and hashlib.sha256(got.tobytes()).digest() == h.tobytes(), f"array of {len(a)} samples"
+    if os.path.exists(make_svbvec.HARNESS):
+        for a, e in zip(arrs, make_svbvec.encode(arrs, str(tmp_path))):
+            np.testing.assert_array_equal(orc.svb_zd(a), e)
 
 
 @pytest.mark.gpu

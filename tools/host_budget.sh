@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 OUT=${1:-gpurun_out/host_budget}; mkdir -p $OUT
 for n in 1 2 4 16; do
   last=$((n - 1))
-  taskset -c 0-$last timeout 600 python bench.py --no-cpu-baseline --no-store-probe --e2e-seconds 0 --small-batch-seconds 0 --every-batch-launches 0 --pipeline-seconds 3 > $OUT/cpus$n.json 2> $OUT/cpus$n.err
+  taskset -c 0-$last timeout 600 python bench.py --full --no-cpu-baseline --no-store-probe --e2e-seconds 0 --small-batch-seconds 0 --every-batch-launches 0 --pipeline-seconds 3 > $OUT/cpus$n.json 2> $OUT/cpus$n.err
 done
 python - $OUT <<'PY'
 import json, sys

@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from squigulator_amd import model, options  # noqa: E402
-from refvec_cases import REFVEC_CASES  # noqa: E402
+from refvec_cases import LIVE_CMD, LIVE_SEEDS, REFVEC_CASES  # noqa: E402
 
 INPUTS = os.path.join(ROOT, "tests", "golden", "inputs")
 OUT = os.path.join(ROOT, "tests", "golden", "refvec")
@@ -105,7 +105,7 @@ def main():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     os.makedirs(OUT, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
-        for cid, cmd in REFVEC_CASES:
+        for cid, cmd in REFVEC_CASES + [(f"live_seed{s}", LIVE_CMD.format(seed=s)) for s in LIVE_SEEDS]:
             reads, k = run_harness(cmd, tmp)
             np.savez_compressed(os.path.join(OUT, cid + ".npz"), cmd=np.array(cmd), k=np.array(k), **pack(reads))
             print(f"{cid}: {len(reads)} reads, {sum(len(r['sig']) for r in reads)} samples")

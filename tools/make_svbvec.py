@@ -4,8 +4,10 @@
 
 Runs only where /root/reference is mounted.  Writes tests/golden/svb/svb_cases.npz: a set of int16 arrays
 (simulated signals from the committed refvec fixtures plus adversarial ones: empty, length 1..9, constant,
-full-range jumps that need 3-byte codes, random) and the bytes the library produces for each.  Data only.
+full-range jumps that need 3-byte codes, random) and the bytes the library produces for each; tests/golden/svb/svb_live.npz: the
+lengths and SHA-256 digests of its bytes for the randomised arrays of live_cases().  Data only.
 usage: python tools/make_svbvec.py"""
+import hashlib
 import os
 import struct
 import subprocess
@@ -36,31 +38,49 @@ def cases():
     return out
 
 
-def main():
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
-    os.makedirs(OUT, exist_ok=True)
-    arrs = cases()
-    with tempfile.TemporaryDirectory() as tmp:
-        fin, fout, cfg = (os.path.join(tmp, x) for x in ("in.bin", "out.bin", "cfg.txt"))
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<i", len(arrs)))
-            for a in arrs:
-                f.write(struct.pack("<q", len(a)))
-                f.write(a.tobytes())
-        with open(cfg, "w") as f:
-            f.write(f"svb_in={fin}\nsvb_out={fout}\n")
-        subprocess.check_call([HARNESS, cfg])
-        buf = open(fout, "rb").read()
+def live_cases():
+    """the randomised arrays of tests/test_svb.py::test_live_against_slow5lib_when_reference_is_mounted"""
+    rng = np.random.default_rng(7)
+    arrs = [rng.integers(-32768, 32768, int(n)).astype(np.int16) for n in rng.integers(0, 5000, 20)]
+    arrs += [(rng.integers(200, 900) + 50 * rng.standard_normal(int(n))).astype(np.int16) for n in rng.integers(1, 50000, 10)]
+    return arrs
+
+
+def encode(arrs, tmp):
+    """the reference's svb-zd bytes of every array (the harness' svb_in/svb_out mode)"""
+    fin, fout, cfg = (os.path.join(tmp, x) for x in ("in.bin", "out.bin", "cfg.txt"))
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<i", len(arrs)))
+        for a in arrs:
+            f.write(struct.pack("<q", len(a)))
+            f.write(a.tobytes())
+    with open(cfg, "w") as f:
+        f.write(f"svb_in={fin}\nsvb_out={fout}\n")
+    subprocess.check_call([HARNESS, cfg])
+    buf = open(fout, "rb").read()
     p = 0
     enc = []
     for _ in arrs:
         (nb,) = struct.unpack_from("<q", buf, p); p += 8
         enc.append(np.frombuffer(buf, np.uint8, nb, p).copy()); p += nb
     assert p == len(buf)
+    return enc
+
+
+def main():
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    os.makedirs(OUT, exist_ok=True)
+    arrs = cases()
+    with tempfile.TemporaryDirectory() as tmp:
+        enc = encode(arrs, tmp)
+        live = encode(live_cases(), tmp)
     np.savez_compressed(os.path.join(OUT, "svb_cases.npz"),
                         lens=np.array([len(a) for a in arrs], np.int64), sig=np.concatenate(arrs),
                         enc_lens=np.array([len(e) for e in enc], np.int64), enc=np.concatenate(enc))
     print(f"{len(arrs)} arrays, {sum(len(a) for a in arrs)} samples -> {sum(len(e) for e in enc)} bytes")
+    # the live arrays' encodings as digests (random signals: the bytes themselves would not compress)
+    np.savez_compressed(os.path.join(OUT, "svb_live.npz"), enc_lens=np.array([len(e) for e in live], np.int64),
+                        enc_sha256=np.array([np.frombuffer(hashlib.sha256(e.tobytes()).digest(), np.uint8) for e in live]))
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ src, dst = sys.argv[1], sys.argv[2]
 os.makedirs(os.path.dirname(dst) or ".", exist_ok=True)
 shutil.copy(os.path.join(src, "trace_kernel_stats.csv"), dst + "_kernel_stats.csv")
 lines = ["# rocprofv3 summary (" + os.path.basename(src) + ")", "",
-         "command: `python bench.py` (the driver's default run) under `rocprofv3 --kernel-trace --stats` (durations); the counters come from",
+         "command: `python bench.py --full` under `rocprofv3 --kernel-trace --stats` (durations); the counters come from",
          "three separate `--pmc` passes of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-store-probe`.", "",
          "## kernel durations (--kernel-trace --stats)", "", "| kernel | calls | avg us | % |", "|---|---|---|---|"]
 for r in csv.DictReader(open(os.path.join(src, "trace_kernel_stats.csv"))):
