@@ -234,16 +234,29 @@ typedef struct sqg_blow5 sqg_blow5_t;
  * (sqg_batch_blow5_records) and the host's part is one PCIe copy and one pwrite(), made behind the caller while the next batch is fetched.  (A deflate block with the fixed Huffman
  * code would be larger, not smaller: svb-zd bytes are nearly uniform, and that code spends 8-9 bits on a literal.) */
 #define SQG_BLOW5_STORED 0x10000u
-/* ... on n files instead of one (with SQG_BLOW5_STORED; n <= 255): `path` x.blow5 names x.0.blow5 ... x.<n-1>.blow5, each a BLOW5 file of its own
+/* SQG_BLOW5_HUFFMAN: the same records, each in a zlib stream of two DYNAMIC-Huffman blocks (RFC 1951 BTYPE 10), literals only -- a valid
+ * BLOW5 file (record method still 1, zlib) that any inflate reads back to the same records, in other bytes than the reference's: about as
+ * many as its zlib level 6 writes, a quarter fewer than SQG_BLOW5_STORED.  Record = u64 compressed size | 78 01 | block A | block B (final) |
+ * Adler-32 (big endian) of the raw record.  Block A codes the raw bytes [0, H + min(S, 4 + ceil(count / 4))) -- the head (u16 idlen | id |
+ * u32 read_group | 4 f64 | u64 S), the svb-zd count and its key bytes --, block B the rest: the svb-zd data bytes and the trailer; H =
+ * 2 + idlen + 4 + 32 + 8, S the svb-zd bytes, count the encoding's own first u32 (the read's samples).  Each block: HLIT 0 (257 codes: the
+ * bytes and end of block), HDIST 1 (two distance codes of length 1), canonical codes of at most 15 bits (code-length code: 7), lengths
+ * run-length coded with 16/17/18; one deterministic construction, stated in squigulator_amd/csrc/kh_huff.h, so that the host encoder
+ * (sqg_blow5_write) and the device's (sqg_batch_blow5_records, sqg_blow5_write_batch) write the same bytes.  Not with SQG_BLOW5_STORED
+ * (SQG_EINVAL); with SQG_BLOW5_SHARDS(n) as the stored mode.  sqg_blow5_write codes on the writer's host threads; sqg_blow5_write_batch
+ * takes the records coded on the device (a batch with a read id over 4096 bytes: coded on the host, the same bytes) and writes them
+ * behind the caller as the stored mode does. */
+#define SQG_BLOW5_HUFFMAN 0x20000u
+/* ... on n files instead of one (with SQG_BLOW5_STORED or SQG_BLOW5_HUFFMAN; n <= 255): `path` x.blow5 names x.0.blow5 ... x.<n-1>.blow5, each a BLOW5 file of its own
  * (header, records, end marker); every batch's reads are dealt out to them in n contiguous ranges, read_number and start_time stay the
  * job's.  What bounds the stored mode is the file: one file of a tmpfs takes 6.9 GB/s from any number of writers, n files n times that
  * (tools/io_probe.cpp) -- the way a run that writes many BLOW5 files (as the sequencers do) scales its sink.  sqg_blow5_close reports the
  * files' sizes added up. */
 #define SQG_BLOW5_SHARDS(n) (((uint32_t)(n) & 0xffu) << 24)
-int  sqg_blow5_open(const char *path, const sqg_profile_t *profile, uint32_t flags /* SQG_RNA | SQG_R10 | SQG_ONT | SQG_BLOW5_STORED | SQG_BLOW5_SHARDS(n) */,
+int  sqg_blow5_open(const char *path, const sqg_profile_t *profile, uint32_t flags /* SQG_RNA | SQG_R10 | SQG_ONT | SQG_BLOW5_STORED or SQG_BLOW5_HUFFMAN | SQG_BLOW5_SHARDS(n) */,
                     int32_t threads, sqg_blow5_t **out);
-/* The batch's records as SQG_BLOW5_STORED writes them, framed on the device around its svb-zd encodings (compressing the batch first
- * if need be) and copied to pinned host memory of the context: *records (valid until the next-but-one call on this context), *n_bytes, and --
+/* The batch's records as SQG_BLOW5_STORED writes them -- as SQG_BLOW5_HUFFMAN writes them when `flags` holds that bit --, framed on the
+ * device around its svb-zd encodings (compressing the batch first if need be) and copied to pinned host memory of the context: *records (valid until the next-but-one call on this context), *n_bytes, and --
  * rec_off may be NULL -- [n_reads+1] offsets of the records in it.  read_number0 / start_time0: records and samples written before
  * this batch (src/sim.c:602).  Read ids of at most 4096 bytes. */
 int  sqg_batch_blow5_records(sqg_ctx_t *ctx, sqg_batch_t *b, const sqg_profile_t *profile, uint32_t flags, const char *read_ids,

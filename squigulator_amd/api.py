@@ -74,6 +74,7 @@ class CSample(C.Structure):
 
 SAMPLE_DNA, SAMPLE_RNA, SAMPLE_CDNA, SAMPLE_TRUNC, SAMPLE_FULL = 0, 1, 2, 4, 8
 BLOW5_STORED = 0x10000          # include/sqg.h SQG_BLOW5_STORED (flags of sqg_blow5_open)
+BLOW5_HUFFMAN = 0x20000         # include/sqg.h SQG_BLOW5_HUFFMAN (flags of sqg_blow5_open and sqg_batch_blow5_records)
 
 EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_device_count",
            "sqg_batch_stage", "sqg_batch_run", "sqg_batch_wait", "sqg_fetch_signal", "sqg_fetch_dwell",
@@ -90,7 +91,7 @@ DEV_KNOBS = ("SQG_SEPARATE_DWELL", "SQG_EVENTS_WIDE_MAX", "SQG_MID_SPLIT", "SQG_
              "SQG_LEAN_DYNLDS", "SQG_FIX_INLINE", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_OVERLAP", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_LEAN_EPL", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_PHC_ABL", "SQG_PHC_GRID", "SQG_NO_DRAW_AHEAD",
-             "SQG_CU_SPLIT", "SQG_NO_FOLD", "SQG_NO_WHOLE_LINKS", "SQG_NO_PLACE")
+             "SQG_CU_SPLIT", "SQG_NO_FOLD", "SQG_NO_WHOLE_LINKS", "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS")
 
 _libs = {}                  # absolute path -> loaded library
 LOADED_PATH = None          # the library the last load_library() call opened (bench.py prints it with its hash)
@@ -260,14 +261,17 @@ class Blow5Writer:
     """The library's native BLOW5 writer (sqg_blow5_*): header, record framing and zlib on host threads; the signal field is
     the svb-zd encoding made on the device.  Pure host code: write() works without a GPU."""
 
-    def __init__(self, path: str, profile: P.Profile, flags: int, threads: int = 0, lib_path: str | None = None, stored: bool = False, shards: int = 1):
+    def __init__(self, path: str, profile: P.Profile, flags: int, threads: int = 0, lib_path: str | None = None, stored: bool = False, shards: int = 1,
+                 huffman: bool = False):
         """stored: SQG_BLOW5_STORED -- the records in zlib streams of stored blocks, framed on the device by write_batch (include/sqg.h);
-        shards > 1: SQG_BLOW5_SHARDS -- that many files (self.paths), each with a contiguous range of every batch's reads"""
+        huffman: SQG_BLOW5_HUFFMAN -- the records in zlib streams of two dynamic-Huffman blocks, coded on the device by write_batch and on
+        the host threads by write (not with stored);
+        shards > 1: SQG_BLOW5_SHARDS -- that many files (self.paths), each with a contiguous range of every batch's reads (stored or huffman)"""
         self.L = load_library(lib_path)
         self.h = C.c_void_p()
         cp = CProfile(*profile.as_tuple())
         self.paths = [path] if shards <= 1 else [(path[:-6] + f".{i}.blow5") if path.endswith(".blow5") else f"{path}.{i}" for i in range(shards)]
-        rc = self.L.sqg_blow5_open(os.fsencode(path), C.byref(cp), (flags & (P.SQ_RNA | P.SQ_R10 | P.SQ_ONT)) | (BLOW5_STORED if stored else 0)
+        rc = self.L.sqg_blow5_open(os.fsencode(path), C.byref(cp), (flags & (P.SQ_RNA | P.SQ_R10 | P.SQ_ONT)) | (BLOW5_STORED if stored else 0) | (BLOW5_HUFFMAN if huffman else 0)
                                    | ((shards & 0xff) << 24 if shards > 1 else 0), threads, C.byref(self.h))
         if rc != 0:
             raise SqgError(rc, "sqg_blow5_open", path)
@@ -391,7 +395,8 @@ class Batch:
         return out
 
     def blow5_records(self, profile, flags: int, read_ids, read_number0: int = 0, start_time0: int = 0):
-        """the batch's BLOW5 records in stored-block zlib streams, framed on the device (sqg_batch_blow5_records) -> (bytes copy, offsets)"""
+        """the batch's BLOW5 records, framed on the device (sqg_batch_blow5_records) -> (bytes copy, offsets): in stored-block zlib streams,
+        or -- BLOW5_HUFFMAN in flags -- in streams of two dynamic-Huffman blocks"""
         blob = b"".join(read_ids)
         ioff = np.zeros(len(read_ids) + 1, np.int64)
         ioff[1:] = np.cumsum([len(r) for r in read_ids])

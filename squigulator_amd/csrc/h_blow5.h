@@ -19,8 +19,12 @@
 // deflate's output -- a valid BLOW5 file with the reference's records that any slow5lib reads, 1.3 instead of 0.97 bytes per sample, not
 // the reference's bytes -- framed on the device (k_blow5.h, sqg_batch_blow5_records) and written behind the caller's back while the next batch's
 // records cross PCIe: the sink at the speed of the file system for hosts that do not need `cmp`-identity (zlib at 28 MB/s per thread is what bounds the default mode).
+// SQG_BLOW5_HUFFMAN: the same records, each in a zlib stream of two dynamic-Huffman blocks (kh_huff.h: format and construction) -- about the
+// reference's size, a quarter smaller than stored blocks -- on the stored mode's path: coded on the device (k_blow5_huff_*) by
+// sqg_blow5_write_batch, on the host threads (blow5_record_huff, the same bytes) by sqg_blow5_write.
 #pragma once
 #include "h_cpus.h"
+#include "kh_huff.h"
 
 #include <zlib.h>
 #include <unistd.h>
@@ -30,7 +34,7 @@
 #endif
 struct sqg_blow5 {
     struct Shard { FILE* fp = nullptr; unsigned long long n_bytes = 0; };
-    std::vector<Shard> sh;               // the files: one, or -- SQG_BLOW5_SHARDS(n), stored mode -- n of them (path.0.blow5 ...), each a BLOW5 file of its own
+    std::vector<Shard> sh;               // the files: one, or -- SQG_BLOW5_SHARDS(n), stored or Huffman mode -- n of them (path.0.blow5 ...), each a BLOW5 file of its own
     FILE* fp = nullptr;                  // (= sh[0].fp)
     sqg_profile_t profile{};
     uint32_t flags = 0;
@@ -39,12 +43,23 @@ struct sqg_blow5 {
     unsigned long long n_samples = 0;    // samples written: the next start_time (core->n_samples, src/sim.c:602)
     unsigned long long n_bytes = 0;      // file bytes so far (one file: = sh[0].n_bytes while it is being written; all files at close)
     bool stored = false;                 // SQG_BLOW5_STORED: the records' zlib streams are stored blocks (valid BLOW5, not the reference's bytes)
+    bool huffman = false;                // SQG_BLOW5_HUFFMAN: ... two dynamic-Huffman blocks (kh_huff.h; valid BLOW5, not the reference's bytes)
+    int maxbits = B5H_MAXBITS;           // ... their codes' length cap (blow5_huff_maxbits)
     std::thread bg;                      // stored mode: the write of the previous batch's records, running behind the caller
     int bg_bad = 0;                      // ... and whether it failed (read after the join)
     bool failed = false;                 // a write came up short: records of an unfinished batch are on disk, nothing more is written
     std::string err;
     sqg_ctx* bound = nullptr;            // the context whose pinned records the background write reads (registered there: sqg_destroy and the next filler of that buffer drain it)
 };
+
+// the length cap of the Huffman codes: deflate's 15; the development build lowers it for tests (SQG_TEST_B5_MAXBITS, 9-14), so that
+// natural records go through the length limiter
+static int blow5_huff_maxbits() {
+#ifdef SQG_DEV_ENV
+    if (const char* v = SQG_DEV_ENV("SQG_TEST_B5_MAXBITS")) { const int m = atoi(v); if (m >= 9 && m < B5H_MAXBITS) return m; }
+#endif
+    return B5H_MAXBITS;
+}
 
 extern "C" const char* sqg_blow5_last_error(const sqg_blow5_t* w) { return w ? w->err.c_str() : ""; }
 
@@ -82,10 +97,12 @@ extern "C" int sqg_blow5_open(const char* path, const sqg_profile_t* profile, ui
     if (!(profile->sample_rate > 0) || profile->sample_rate > 1000000000.0) return SQG_EINVAL;     // src/gensig.c:117-120
     sqg_blow5* w = new (std::nothrow) sqg_blow5();
     if (!w) return SQG_ENOMEM;
-    w->profile = *profile; w->flags = flags; w->stored = (flags & SQG_BLOW5_STORED) != 0;
+    w->profile = *profile; w->flags = flags; w->stored = (flags & SQG_BLOW5_STORED) != 0; w->huffman = (flags & SQG_BLOW5_HUFFMAN) != 0;
+    w->maxbits = blow5_huff_maxbits();
     w->threads = threads > 0 ? threads : std::min(16, usable_cpus());
+    if (w->stored && w->huffman) { delete w; return SQG_EINVAL; }  // (one record compression per file)
     const int ns = std::max(1, (int)(flags >> 24));
-    if (ns > 1 && !w->stored) { delete w; return SQG_EINVAL; }     // (several files: the stored-block mode only)
+    if (ns > 1 && !w->stored && !w->huffman) { delete w; return SQG_EINVAL; }     // (several files: the stored-block and Huffman modes only)
     const std::string h = blow5_header(*profile, flags);
     auto fail = [&](const char* what, const std::string& pth) {
         fprintf(stderr, "[sqg] sqg_blow5_open: cannot %s %s: %s\n", what, pth.c_str(), strerror(errno));   // (no writer to ask: the reason goes to stderr, the code says I/O)
@@ -140,11 +157,9 @@ static bool blow5_record(z_stream& zs, std::vector<uint8_t>& raw, std::vector<ui
     return true;
 }
 
-// RFC 1950 / 1951 by hand: 78 01 | stored blocks of at most 65535 bytes | Adler-32.  The same bytes k_blow5_frame writes on the device.
-// (appended to `dst`, or -- at_ptr != null -- written there: 8 + 2 + 5 ceil(R / 65535) + R + 4 bytes for a raw record of R bytes)
-static void blow5_record_stored(std::vector<uint8_t>& raw, std::vector<uint8_t>& dst, const sqg_blow5* w, const char* id, size_t id_len,
-                                double offset, double median_before, const uint8_t* svb, uint64_t svb_bytes, int32_t read_number, uint64_t start_time,
-                                uint8_t* at_ptr = nullptr) {
+// the raw record (slow5_rec_to_mem's layout) in `raw`
+static void blow5_raw(std::vector<uint8_t>& raw, const sqg_blow5* w, const char* id, size_t id_len, double offset, double median_before,
+                      const uint8_t* svb, uint64_t svb_bytes, int32_t read_number, uint64_t start_time) {
     raw.clear();
     auto put = [&](const void* p, size_t n) { const uint8_t* q = (const uint8_t*)p; raw.insert(raw.end(), q, q + n); };
     const uint16_t idl = (uint16_t)id_len;
@@ -156,6 +171,79 @@ static void blow5_record_stored(std::vector<uint8_t>& raw, std::vector<uint8_t>&
     put(&one, 8); put(&ch, 1);
     put(&median_before, 8); put(&read_number, 4); put(&mux, 1); put(&start_time, 8);
     if (w->flags & SQG_ONT) { const uint8_t end_reason = 0; put(&end_reason, 1); }
+}
+
+// Adler-32 of the raw record, 5552 bytes between the reductions (zlib's NMAX)
+static uint32_t blow5_adler(const std::vector<uint8_t>& raw) {
+    const size_t R = raw.size();
+    uint32_t a = 1, b2 = 0;
+    for (size_t r = 0; r < R; ) {
+        const size_t e = std::min(R, r + 5552);
+        for (; r < e; r++) { a += raw[r]; b2 += a; }
+        a %= 65521u; b2 %= 65521u;
+    }
+    return b2 << 16 | a;
+}
+
+// SQG_BLOW5_HUFFMAN: where block A ends -- the head, the svb-zd count and its key bytes (kh_huff.h)
+static inline size_t blow5_huff_cut(size_t id_len, const uint8_t* svb, uint64_t svb_bytes) {
+    const size_t H = 2 + id_len + 4 + 32 + 8;
+    if (svb_bytes < 4) return H + (size_t)svb_bytes;
+    uint32_t count;
+    memcpy(&count, svb, 4);
+    const uint64_t keys = 4 + ((uint64_t)count + 3) / 4;
+    return H + (size_t)std::min<uint64_t>(keys, svb_bytes);
+}
+
+// SQG_BLOW5_HUFFMAN: the raw record as 78 01 | dynamic-Huffman block A [0, cut) | final block B [cut, R) | Adler-32 (kh_huff.h), appended
+// to `dst` with its size prefix.  The same bytes k_blow5_huff_size / k_blow5_huff_encode write on the device.
+static void blow5_record_huff(const std::vector<uint8_t>& raw, size_t cut, int maxbits, std::vector<uint8_t>& dst) {
+    const size_t R = raw.size();
+    uint32_t freq[2][B5H_SYMS];
+    memset(freq, 0, sizeof freq);
+    for (size_t r = 0; r < cut; r++) freq[0][raw[r]]++;
+    for (size_t r = cut; r < R; r++) freq[1][raw[r]]++;
+    B5HuffCode code[2];
+    B5HuffWork wk;
+    uint16_t sorted[B5H_SYMS];
+    unsigned long long bits = 0;
+    for (int k = 0; k < 2; k++) {
+        freq[k][256] = 1;
+        const int m = b5h_prepare(freq[k], B5H_SYMS);
+        b5h_sort(freq[k], B5H_SYMS, sorted);
+        bits += b5h_build(freq[k], sorted, m, maxbits, k, &code[k], &wk);
+    }
+    const uint64_t csize = 2 + (bits + 7) / 8 + 4;
+    const size_t at = dst.size();
+    dst.resize(at + 8 + csize);
+    uint8_t* o = dst.data() + at;
+    memcpy(o, &csize, 8); o[8] = 0x78; o[9] = 0x01; o += 10;
+    unsigned long long acc = 0;
+    int nacc = 0;
+    auto put = [&](uint32_t v, int nb) {
+        acc |= (unsigned long long)v << nacc; nacc += nb;
+        if (nacc >= 32) { o[0] = (uint8_t)acc; o[1] = (uint8_t)(acc >> 8); o[2] = (uint8_t)(acc >> 16); o[3] = (uint8_t)(acc >> 24); o += 4; acc >>= 32; nacc -= 32; }
+    };
+    for (int k = 0; k < 2; k++) {
+        const B5HuffCode& c = code[k];
+        for (uint32_t j = 0; j < c.hdr_bits; j += 8) put(c.hdr[j / 8], (int)std::min<uint32_t>(8, c.hdr_bits - j));
+        for (size_t r = k ? cut : 0, e = k ? R : cut; r < e; r++) { const uint32_t x = c.code[raw[r]]; put(x & 0xffffu, (int)(x >> 16)); }
+        put(c.code[256] & 0xffffu, (int)(c.code[256] >> 16));
+    }
+    for (; nacc > 0; nacc -= 8) { *o++ = (uint8_t)acc; acc >>= 8; }
+    const uint32_t ad = blow5_adler(raw);
+    o[0] = (uint8_t)(ad >> 24); o[1] = (uint8_t)(ad >> 16); o[2] = (uint8_t)(ad >> 8); o[3] = (uint8_t)ad;
+}
+
+// RFC 1950 / 1951 by hand: 78 01 | stored blocks of at most 65535 bytes | Adler-32.  The same bytes k_blow5_frame writes on the device.
+// (appended to `dst`, or -- at_ptr != null -- written there: 8 + 2 + 5 ceil(R / 65535) + R + 4 bytes for a raw record of R bytes)
+// With SQG_BLOW5_HUFFMAN in w->flags: the Huffman record instead (blow5_record_huff; appended, at_ptr must be null) -- the CPU backend's
+// sqg_batch_blow5_records frames through here with the caller's flags.
+static void blow5_record_stored(std::vector<uint8_t>& raw, std::vector<uint8_t>& dst, const sqg_blow5* w, const char* id, size_t id_len,
+                                double offset, double median_before, const uint8_t* svb, uint64_t svb_bytes, int32_t read_number, uint64_t start_time,
+                                uint8_t* at_ptr = nullptr) {
+    blow5_raw(raw, w, id, id_len, offset, median_before, svb, svb_bytes, read_number, start_time);
+    if (w->flags & SQG_BLOW5_HUFFMAN) { blow5_record_huff(raw, blow5_huff_cut(id_len, svb, svb_bytes), w->maxbits, dst); return; }
     const size_t R = raw.size(), nb = (R + 65534) / 65535;
     const uint64_t csize = 2 + 5 * nb + R + 4;
     uint8_t* o = at_ptr;
@@ -165,19 +253,13 @@ static void blow5_record_stored(std::vector<uint8_t>& raw, std::vector<uint8_t>&
         o = dst.data() + at;
     }
     memcpy(o, &csize, 8); o[8] = 0x78; o[9] = 0x01; o += 10;
-    uint32_t a = 1, b2 = 0;
     for (size_t k = 0; k < nb; k++) {
         const size_t r0 = k * 65535, len = std::min<size_t>(65535, R - r0);
         o[0] = k + 1 == nb ? 1 : 0; o[1] = (uint8_t)len; o[2] = (uint8_t)(len >> 8); o[3] = (uint8_t)~len; o[4] = (uint8_t)(~len >> 8);
         memcpy(o + 5, raw.data() + r0, len);
         o += 5 + len;
     }
-    for (size_t r = 0; r < R; ) {                                  // Adler-32, 5552 bytes between the reductions (zlib's NMAX)
-        const size_t e = std::min(R, r + 5552);
-        for (; r < e; r++) { a += raw[r]; b2 += a; }
-        a %= 65521u; b2 %= 65521u;
-    }
-    const uint32_t ad = b2 << 16 | a;
+    const uint32_t ad = blow5_adler(raw);
     o[0] = (uint8_t)(ad >> 24); o[1] = (uint8_t)(ad >> 16); o[2] = (uint8_t)(ad >> 8); o[3] = (uint8_t)ad;
 }
 
@@ -291,6 +373,49 @@ extern "C" int sqg_blow5_write(sqg_blow5_t* w, int32_t n, const char* read_ids, 
         w->n_bytes += (unsigned long long)ro[(size_t)n]; w->n_reads += n; w->n_samples = run;
         return SQG_OK;
     }
+    if (w->huffman) {
+        // a Huffman record's size is known only once it is coded: per-thread buffers, put together behind each other
+        std::vector<std::vector<uint8_t>> outs((size_t)nth);
+        std::vector<std::vector<int64_t>> ends((size_t)nth);
+        auto code = [&](int t) {
+            const int lo = (int)((long long)n * t / nth), hi = (int)((long long)n * (t + 1) / nth);
+            std::vector<uint8_t> raw;
+            std::vector<uint8_t>& dst = outs[(size_t)t];
+            dst.reserve((size_t)(svb_off[hi] - svb_off[lo]) + (size_t)(hi - lo) * 700);
+            for (int i = lo; i < hi; i++) {
+                const size_t il = (size_t)(id_off[i + 1] - id_off[i]);
+                const uint64_t sb = (uint64_t)(svb_off[i + 1] - svb_off[i]);
+                blow5_raw(raw, w, read_ids + id_off[i], il, offset[i], median_before[i], svb + svb_off[i], sb, (int32_t)(w->n_reads + i), start[(size_t)i]);
+                blow5_record_huff(raw, blow5_huff_cut(il, svb + svb_off[i], sb), w->maxbits, dst);
+                ends[(size_t)t].push_back((int64_t)dst.size());
+            }
+        };
+        if (nth == 1) code(0);
+        else {
+            std::vector<std::thread> th;
+            for (int t = 0; t < nth; t++) { try { th.emplace_back(code, t); } catch (const std::system_error&) { code(t); } }
+            for (auto& t : th) t.join();
+        }
+        std::vector<int64_t> ro((size_t)n + 1, 0);
+        size_t total = 0;
+        for (int t = 0, i = 0; t < nth; t++) {
+            for (const int64_t e : ends[(size_t)t]) ro[(size_t)++i] = (int64_t)total + e;
+            total += outs[(size_t)t].size();
+        }
+        std::vector<uint8_t> all;
+        if (nth == 1) all.swap(outs[0]);
+        else {
+            all.resize(total);
+            for (int t = 0; t < nth; t++) { const int lo = (int)((long long)n * t / nth); memcpy(all.data() + ro[(size_t)lo], outs[(size_t)t].data(), outs[(size_t)t].size()); }
+        }
+        if (!blow5_append_records(w, all.data(), ro.data(), n, /*async=*/false)) {
+            w->failed = true;
+            w->err = std::string("sqg_blow5_write: short write (") + strerror(errno) + "): the file is incomplete";
+            return SQG_EIO;
+        }
+        w->n_bytes += (unsigned long long)total; w->n_reads += n; w->n_samples = run;
+        return SQG_OK;
+    }
     std::vector<std::vector<uint8_t>> outs((size_t)nth);
     std::vector<int> bad((size_t)nth, 0);
     auto work = [&](int t) {
@@ -334,11 +459,11 @@ extern "C" int sqg_blow5_write_batch(sqg_blow5_t* w, sqg_ctx_t* c, sqg_batch_t* 
     sqg_result_t res;
     int rc = sqg_batch_wait(c, b, &res);
     if (rc) { w->err = sqg_last_error(c); return rc; }
-    bool device_frames = w->stored;
+    bool device_frames = w->stored || w->huffman;
     if (device_frames && read_ids && id_off)
         for (int i = 0; i < res.n_reads; i++) if (id_off[i + 1] - id_off[i] > B5_ID_MAX) { device_frames = false; break; }
-    // (a read id longer than the framing kernel's LDS header, 4096 bytes: this batch is framed on the host below -- sqg_blow5_write takes ids
-    // up to 65535 bytes in stored mode as well -- instead of failing mid-file)
+    // (a read id longer than the framing kernels' LDS header, 4096 bytes: this batch is framed on the host below -- sqg_blow5_write takes ids
+    // up to 65535 bytes in the stored and Huffman modes as well, same bytes -- instead of failing mid-file)
     if (device_frames) {
         // the records come framed from the device (sqg_batch_blow5_records): one copy over PCIe, one write
         if (w->bound && w->bound != c) { blow5_ctx_hook(w, false); blow5_unbind(w); }      // (the writer moves to another context: nothing of the old one is read any more)
@@ -375,10 +500,11 @@ extern "C" int sqg_blow5_close(sqg_blow5_t* w, int64_t* n_bytes) {
     for (size_t q = 0; q < w->sh.size(); q++) {
         sqg_blow5::Shard& f = w->sh[q];
         if (!f.fp) continue;
-        if (!w->stored) f.n_bytes = w->n_bytes;                      // (one file, written through the FILE)
+        const bool pw = w->stored || w->huffman;                     // (records written with pwrite(), per file)
+        if (!pw) f.n_bytes = w->n_bytes;                             // (one file, written through the FILE)
         if (!w->failed) {
             // slow5_eof_fwrite, slow5.c:4206 (stored mode: the records went out with pwrite(): the marker goes behind them the same way)
-            const bool ok = w->stored ? (fflush(f.fp) == 0 && blow5_copy_out(fileno(f.fp), reinterpret_cast<const uint8_t*>("5WOLB"), 5, (off_t)f.n_bytes))
+            const bool ok = pw ? (fflush(f.fp) == 0 && blow5_copy_out(fileno(f.fp), reinterpret_cast<const uint8_t*>("5WOLB"), 5, (off_t)f.n_bytes))
                                       : fwrite("5WOLB", 1, 5, f.fp) == 5;
             if (!ok) rc = SQG_EIO; else f.n_bytes += 5;
         }

@@ -203,6 +203,9 @@ struct sqg_ctx {
     int b5_flip = 0;                                           //     them used alternately: a result stays valid over the NEXT call (a writer copies it out behind that call)
     uint8_t* h_b5meta = nullptr; size_t h_b5meta_cap = 0;      // ... pinned staging of the upload
     std::vector<int64_t> b5_rec_off;
+    B5HuffCode* d_b5tab = nullptr; size_t b5tab_cap = 0;       // SQG_BLOW5_HUFFMAN: the two codes of every record (k_blow5_huff_size -> k_blow5_huff_encode) ...
+    unsigned long long* d_b5size = nullptr; size_t b5size_cap = 0;   // ... and the records' sizes
+    std::vector<unsigned long long> b5_size;
     // a stored-mode writer whose background write still reads h_b5out[b5_reader_buf] (h_blow5.h registers itself here): drained before that
     // buffer is filled again by anybody, and before the context goes (the thread read memory the writer did not own)
     // placement calibration: the scatter pass runs in one of several modes (825 ... 1130 us per 32768 10-kb reads) for the life of a slot's `evrec` allocation

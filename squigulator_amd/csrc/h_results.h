@@ -166,13 +166,18 @@ extern "C" int sqg_fetch_svb(sqg_ctx_t* c, sqg_batch_t* b, uint8_t* dst) {
     return SQG_OK;
 }
 
+static int blow5_huff_maxbits();                            // (h_blow5.h: the Huffman codes' length cap, which the host encoder uses as well)
+
 // The batch's BLOW5 records -- slow5_rec_to_mem's layout (slow5lib/src/slow5.c:3928-4072) around the device's svb-zd bytes, each in a zlib
-// stream of stored blocks (k_blow5.h) -- framed on the device and copied to pinned host memory of the context: what a writer appends to
-// the file as it is.  Compresses the batch first unless its encodings are still the context's.
+// stream of stored blocks (k_blow5.h) or, SQG_BLOW5_HUFFMAN, of two dynamic-Huffman blocks (k_blow5_huff_*) -- framed on the device and copied
+// to pinned host memory of the context: what a writer appends to the file as it is.  Compresses the batch first unless its encodings are
+// still the context's.
 extern "C" int sqg_batch_blow5_records(sqg_ctx_t* c, sqg_batch_t* b, const sqg_profile_t* profile, uint32_t flags, const char* read_ids,
                                        const int64_t* id_off, int64_t read_number0, uint64_t start_time0,
                                        const uint8_t** records, int64_t* n_bytes, const int64_t** rec_off) {
     if (!c || !b || !b->ran || !profile || !records || !n_bytes || (b->n > 0 && (!read_ids || !id_off))) return SQG_EINVAL;
+    const bool huff = (flags & SQG_BLOW5_HUFFMAN) != 0;
+    if (huff && (flags & SQG_BLOW5_STORED)) { c->err = "sqg_batch_blow5_records: SQG_BLOW5_STORED and SQG_BLOW5_HUFFMAN are exclusive"; return SQG_EINVAL; }
     if (b->run_idx + 2 < c->runs || !slot_is_mine(c, b)) return SQG_ESEQUENCE;
     int rc;
     if (b->n_svb < 0 || b->compress_seq != c->compress_seq) { sqg_svb_t sv; if ((rc = sqg_batch_compress(c, b, &sv))) return rc; }
@@ -184,10 +189,11 @@ extern "C" int sqg_batch_blow5_records(sqg_ctx_t* c, sqg_batch_t* b, const sqg_p
     for (int i = 0; i < n; i++) {
         const int64_t idl = id_off[i + 1] - id_off[i];
         if (idl < 0 || idl > B5_ID_MAX) { c->err = "sqg_batch_blow5_records: read id longer than 4096 bytes (use the host-zlib writer)"; return SQG_EINVAL; }
+        if (huff) continue;                                 // (a Huffman record's size: k_blow5_huff_size below)
         const unsigned long long R = (unsigned long long)(2 + idl + 4 + 32 + 8) + (unsigned long long)(b->h_svboff[i + 1] - b->h_svboff[i]) + (unsigned long long)(30 + (ont ? 1 : 0));
         ro[(size_t)i + 1] = ro[(size_t)i] + (int64_t)b5_stored_size(R);
     }
-    const size_t total = (size_t)ro[(size_t)n];
+    size_t total = (size_t)ro[(size_t)n];
     *records = nullptr; *n_bytes = (int64_t)total;
     if (rec_off) *rec_off = ro.data();
     if (n == 0) return SQG_OK;
@@ -195,7 +201,7 @@ extern "C" int sqg_batch_blow5_records(sqg_ctx_t* c, sqg_batch_t* b, const sqg_p
     const size_t id_bytes = (size_t)(id_off[n] - id_off[0]);
     const size_t o_io = 0, o_ro = o_io + ((size_t)n + 1) * 8, o_of = o_ro + ((size_t)n + 1) * 8, o_md = o_of + (size_t)n * 8, o_id = o_md + (size_t)n * 8, meta = o_id + id_bytes + 16;
     if ((rc = ensure(c, (void**)&c->d_b5meta, &c->b5meta_cap, meta, 1))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_b5out, &c->b5out_cap, total + 64, 1))) return rc;
+    if (!huff && (rc = ensure(c, (void**)&c->d_b5out, &c->b5out_cap, total + 64, 1))) return rc;
     if (c->h_b5meta_cap < meta) {
         if (c->h_b5meta) (void)hipHostFree(c->h_b5meta);
         c->h_b5meta = nullptr; c->h_b5meta_cap = 0;
@@ -208,12 +214,16 @@ extern "C" int sqg_batch_blow5_records(sqg_ctx_t* c, sqg_batch_t* b, const sqg_p
     // the encodings are complete (sqg_batch_compress synchronises) and so is the slot's sig_off (the batch was waited for): the framing needs nothing of
     // the main stream, where the NEXT batch's kernels are queued by now -- a stream of its own, and only that one is waited for
     const hipStream_t bs = c->b5_stream;
-    if (c->h_b5out_cap[fl] < total) {
-        if (c->h_b5out[fl]) (void)hipHostFree(c->h_b5out[fl]);
-        c->h_b5out[fl] = nullptr; c->h_b5out_cap[fl] = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_b5out[fl], total + total / 4, hipHostMallocDefault));
-        c->h_b5out_cap[fl] = total + total / 4;
-    }
+    auto pinned_out = [&]() -> int {
+        if (c->h_b5out_cap[fl] < total) {
+            if (c->h_b5out[fl]) (void)hipHostFree(c->h_b5out[fl]);
+            c->h_b5out[fl] = nullptr; c->h_b5out_cap[fl] = 0;
+            HIPCHK(c, hipHostMalloc(&c->h_b5out[fl], total + total / 4, hipHostMallocDefault));
+            c->h_b5out_cap[fl] = total + total / 4;
+        }
+        return SQG_OK;
+    };
+    if (!huff && (rc = pinned_out())) return rc;
     {
         long long* io = reinterpret_cast<long long*>(c->h_b5meta + o_io);
         for (int i = 0; i <= n; i++) io[i] = (long long)(id_off[i] - id_off[0]);
@@ -230,7 +240,27 @@ extern "C" int sqg_batch_blow5_records(sqg_ctx_t* c, sqg_batch_t* b, const sqg_p
     P.ids = c->d_b5meta + o_id; P.out = c->d_b5out;
     P.digitisation = profile->digitisation; P.range = profile->range; P.sample_rate = profile->sample_rate;
     P.read_number0 = read_number0; P.start_time0 = start_time0; P.ont = ont ? 1 : 0; P.n = n;
-    hipLaunchKernelGGL(k_blow5_frame, dim3((unsigned)n), dim3(256), 0, bs, P);
+    if (huff) {
+        // the codes and the records' sizes first; their scan places the records (and is what the caller's shard split needs)
+        if ((rc = ensure(c, (void**)&c->d_b5tab, &c->b5tab_cap, 2 * (size_t)n, sizeof(B5HuffCode)))) return rc;
+        if ((rc = ensure(c, (void**)&c->d_b5size, &c->b5size_cap, (size_t)n, sizeof(unsigned long long)))) return rc;
+        hipLaunchKernelGGL(k_blow5_huff_size, dim3((unsigned)n), dim3(256), 0, bs, P, c->d_b5tab, c->d_b5size, blow5_huff_maxbits());
+        HIPCHK(c, hipGetLastError());
+        c->b5_size.resize((size_t)n);
+        HIPCHK(c, hipMemcpyAsync(c->b5_size.data(), c->d_b5size, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, bs));
+        HIPCHK(c, hipStreamSynchronize(bs));
+        for (int i = 0; i < n; i++) ro[(size_t)i + 1] = ro[(size_t)i] + (int64_t)c->b5_size[(size_t)i];
+        total = (size_t)ro[(size_t)n];
+        *n_bytes = (int64_t)total;
+        memcpy(c->h_b5meta + o_ro, ro.data(), ((size_t)n + 1) * 8);
+        HIPCHK(c, hipMemcpyAsync(c->d_b5meta + o_ro, c->h_b5meta + o_ro, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, bs));
+        if ((rc = ensure(c, (void**)&c->d_b5out, &c->b5out_cap, total + 64, 1))) return rc;
+        if ((rc = pinned_out())) return rc;
+        P.out = c->d_b5out;
+        hipLaunchKernelGGL(k_blow5_huff_encode, dim3((unsigned)n), dim3(256), 0, bs, P, (const B5HuffCode*)c->d_b5tab);
+    } else {
+        hipLaunchKernelGGL(k_blow5_frame, dim3((unsigned)n), dim3(256), 0, bs, P);
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_b5out[fl], c->d_b5out, total, hipMemcpyDeviceToHost, bs));
     HIPCHK(c, hipStreamSynchronize(bs));

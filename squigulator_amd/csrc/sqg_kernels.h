@@ -14,6 +14,7 @@
 //   k_sample, k_copy_reads   gen_read on the device-resident genome        (src/genread.c:125-370)
 //   k_svb_*       slow5lib's svb-zd signal compression                    (slow5lib/src/slow5_press.c:1055-1087)
 //   k_blow5_frame BLOW5 records (slow5_rec_to_mem's layout) in stored-block zlib streams (slow5lib/src/slow5.c:3928-4072)
+//   k_blow5_huff_* the same records in streams of two dynamic-Huffman blocks (SQG_BLOW5_HUFFMAN; codes built by kh_huff.h)
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
 // (src/rand.h:87-94).  CERTIFIED: a draw is first evaluated with fp32 hardware transcendentals;
