@@ -129,7 +129,7 @@ typedef struct {
 
 /* kernel timings of the batch last waited for, from hipEvents on the context's stream (see sqg_set_phase_timing) */
 typedef struct {
-    float dwell_ms;             /* stand-alone k_dwell (0 when the draws are made inside k_events) */
+    float dwell_ms;             /* always 0: the dwell draws are made inside the event kernels */
     float events_ms;            /* k_events (dwell draws, k-mer ranks, stream hand-out)      */
     float samples_ms;           /* k_scan + k_samples_lean + k_samples<generic> + k_fixup*   */
     float lean_ms;              /* k_samples_lean alone: the dominant, roofline-priced kernel (0 if not launched) */

@@ -87,11 +87,10 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 
 # Environment knobs only the development build of the library reads (csrc/h_common.h: SQG_DEV_ENV; tools/README.md).  The release
 # library ignores them, so a process that sets one -- a test forcing a code path, an A/B script -- gets libsqg_hip_dev.so.
-DEV_KNOBS = ("SQG_SEPARATE_DWELL", "SQG_EVENTS_WIDE_MAX", "SQG_MID_SPLIT", "SQG_SCAN_G4", "SQG_TEST_ORDER_FAULT", "SQG_LEAN_GRID",
-             "SQG_LEAN_DYNLDS", "SQG_FIX_INLINE", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_OVERLAP", "SQG_PART_CLAIMS",
-             "SQG_TEST_DELTA_X", "SQG_LEAN_EPL", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
-             "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_PHC_ABL", "SQG_PHC_GRID", "SQG_NO_DRAW_AHEAD",
-             "SQG_CU_SPLIT", "SQG_NO_FOLD", "SQG_NO_WHOLE_LINKS", "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS")
+DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
+             "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
+             "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS")
 
 _libs = {}                  # absolute path -> loaded library
 LOADED_PATH = None          # the library the last load_library() call opened (bench.py prints it with its hash)

@@ -100,8 +100,8 @@ struct sqg_ctx {
     unsigned long long fix_tickets = 0;            // k_fixup launches so far: the tag of the launch's list entries
     unsigned long long scan_tickets = 0;           // k_scan launches so far: every launch gets a ticket of its own
     // Everything a batch's kernels write lives in one of two SLOTS (batch seq & 1): a batch's results stay valid while
-    // the next one runs (sqg_batch_wait / sqg_fetch_* of batch i do not wait for batch i+1), and with SQG_OVERLAP=1 the
-    // event kernels of batch i+1 (stream) run while the sample kernels of batch i (stream2) are still busy.
+    // the next one runs (sqg_batch_wait / sqg_fetch_* of batch i do not wait for batch i+1), and the fix-ups of batch i
+    // (fix_stream) run while the event kernels of batch i+1 (stream) are busy.
     struct Slot {
         int16_t* d_sig = nullptr; size_t sig_cap = 0;
         long long* d_sigoff = nullptr; size_t reads_cap = 0;
@@ -127,7 +127,7 @@ struct sqg_ctx {
         uint2* cal_prev = nullptr; float cal_prev_ps = 0.f;   // the allocation before the candidate, until the candidate has been measured
         unsigned long long gen = 0;                // bumped whenever a batch starts writing the slot's buffers
         hipEvent_t done = nullptr;                 // recorded after the slot's last kernel (fix-ups included)
-        hipEvent_t sampled = nullptr;              // recorded on stream2 after the slot's sample kernels, before the fix-ups
+        hipEvent_t sampled = nullptr;              // recorded on stream after the slot's sample kernels, before the fix-ups
     } slot[2];
     // What a batch's FIRST event pass writes -- the dwells, the first sample of every 64-event tile, the reads' sample totals -- lives in
     // one of THREE sets (batch run index % 3): the first pass of batch i+1 may run inside the launch sequence of batch i (k_part_hand_count,
@@ -140,9 +140,7 @@ struct sqg_ctx {
         unsigned long long gen = 0;   // bumped whenever a batch starts writing the set
     } cset[3];
     int num_cu = 256;                              // compute units of the device
-    unsigned int* d_zero = nullptr;                // one word that is always zero ("no slices": k_part_hand_count as a counting-only launch, development builds)
     std::deque<sqg_batch*> staged_q;               // staged, not yet run, in staging order (the batch behind the one being run: precount)
-    hipStream_t stream2 = nullptr;                 // the sample kernels (k_samples_lean, generic); == stream unless SQG_OVERLAP=1
     hipStream_t fix_stream = nullptr;              // the FP64 fix-ups of batch i (two small kernels) run next to k_events of batch i+1
     unsigned long long* d_scan_part = nullptr; size_t scan_part_cap = 0;   // k_scan: {ticket, total} per workgroup
     uint32_t* d_link_rows = nullptr; size_t link_rows_cap = 0;   // split chains: one row per link of the running batch
@@ -229,7 +227,6 @@ struct sqg_batch {
     size_t block_bytes = 0, h_n = 0;     // its size; entries of h_sigoff
     uint8_t* d_bases = nullptr;
     ReadDesc* d_reads = nullptr;
-    int* d_blk_read = nullptr;
     int* d_chain_off = nullptr;
     int* d_chain_reads = nullptr;
     int* d_chain_order = nullptr;
@@ -266,7 +263,7 @@ struct sqg_batch {
     long long n_svb = -1;
     unsigned long long compress_seq = 0;
     bool untimed = false;                          // no phase events in this batch (sqg_set_phase_timing): its timings read 0
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // kernel-phase boundaries; [7]: the event side is done
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // kernel-phase boundaries: [0] start, [3] event side done, [4] batch done, [5] / [6] around k_samples_lean ([1], [2], [7]: spare)
     uint8_t* h_meta = nullptr; size_t h_meta_bytes = 0;   // pinned: the host-built arrays of the batch (descriptors, chain lists), uploaded in one copy
     hipEvent_t ev_staged = nullptr;      // recorded on the staging stream after the batch's last staging operation
     unsigned int* d_err = nullptr;       // the batch's own device error word (in d_block; zeroed by the meta upload): batches queued back
@@ -280,7 +277,7 @@ struct sqg_batch {
     int pre_slot = -1;                   // ... which, with one partition, wrote part[] of this slot
     bool carried_precount = false;       // this batch's launch sequence carried its successor's first event pass (k_part_hand_count)
     unsigned long long run_idx = 0;      // how many batches had been run before this one
-    bool ran = false, waited = false, lean_timed = false, dwell_timed = false, fixup_launched = false;
+    bool ran = false, waited = false, lean_timed = false, fixup_launched = false;
     bool staged = false;                 // staging completed: the batch holds a place in the run order
     bool begun = false, other_fresh = false;   // sqg_batch_run_begin has run; the other slot had never held a batch then
 };
@@ -411,7 +408,7 @@ static void skip_abandoned(sqg_ctx* c) {
 static int ensure(sqg_ctx* c, void** p, size_t* cap, size_t need, size_t elem) {
     if (need <= *cap) return SQG_OK;
     size_t ncap = std::max(need + need / 4, *cap + *cap / 2);     // slack: batches of similar size never re-allocate
-    if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream2)); HIPCHK(c, hipStreamSynchronize(c->fix_stream)); HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
+    if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->fix_stream)); HIPCHK(c, hipFree(*p)); *p = nullptr; *cap = 0; }
     HIPCHK(c, hipMalloc(p, ncap * elem));
     *cap = ncap;
     return SQG_OK;
@@ -429,7 +426,6 @@ static int dbg_sync(sqg_ctx* c, const char* what) {
     static const bool on = getenv("SQG_DEBUG_SYNC") != nullptr;
     if (!on) return SQG_OK;
     hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream2);
     if (e == hipSuccess) e = hipStreamSynchronize(c->fix_stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) { c->err = std::string(what) + ": " + hipGetErrorString(e); fprintf(stderr, "[sqg] %s\n", c->err.c_str()); return SQG_EDEVICE; }

@@ -21,9 +21,6 @@ extern "C" int sqg_batch_wait(sqg_ctx_t* c, sqg_batch_t* b, sqg_result_t* res) {
         const unsigned int* const hres = reinterpret_cast<const unsigned int*>(b->h_sigoff + (b->h_n - SQG_HRES_LL));   // k_fixup's report (mapped host memory)
         if (b->fixup_launched) e = hres[0];
         else HIPCHK(c, hipMemcpy(&e, b->d_err, sizeof e, hipMemcpyDeviceToHost));   // the batch's own word: never cleared, never shared
-#if defined(SQG_ABL_EV_NOSTORE) || defined(SQG_ABL_NOSTORE)       /* timing-only ablation builds: results are garbage by design */
-        e = 0;
-#endif
         b->waited = true;
         if (e) {
             c->err = "device reported: " + std::string((e & 1) ? "dwell>65535 " : "") + ((e & 2) ? "read>=UINT32_MAX samples " : "") + ((e & 4) ? "internal length mismatch " : "") + ((e & 8) ? "FP64 fix-up list overflow " : "") + ((e & 32) ? "one k-mer stream asked for >= 2^32 samples by one batch " : "") +
@@ -32,10 +29,9 @@ extern "C" int sqg_batch_wait(sqg_ctx_t* c, sqg_batch_t* b, sqg_result_t* res) {
             b->wait_rc = (e & (12 | 64 | 0x80000000u)) ? SQG_EDEVICE : SQG_EOVERFLOW;
             return b->wait_rc;
         }
-        float d = 0, s = 0, t = 0, ee = 0;
+        float s = 0, t = 0, ee = 0;
         if (!b->untimed) {                                  // (sqg_set_phase_timing: a batch without the phase events reports 0 ms)
-            if (b->dwell_timed) HIPCHK(c, hipEventElapsedTime(&d, b->ev[0], b->ev[1]));
-            HIPCHK(c, hipEventElapsedTime(&ee, b->ev[b->dwell_timed ? 2 : 0], b->ev[3]));
+            HIPCHK(c, hipEventElapsedTime(&ee, b->ev[0], b->ev[3]));
             HIPCHK(c, hipEventElapsedTime(&s, b->ev[3], b->ev[4]));
             HIPCHK(c, hipEventElapsedTime(&t, b->ev[0], b->ev[4]));
         }
@@ -55,7 +51,7 @@ extern "C" int sqg_batch_wait(sqg_ctx_t* c, sqg_batch_t* b, sqg_result_t* res) {
             nfix = cnt[0];                                  // the global list ...
             if (lists) for (int i = 0; i < FIX_SHARDS; i++) nfix += cnt[4 + i];   // ... + the lean kernel's lists (a word per list, written by k_fixup)
         }
-        c->timing.dwell_ms = d; c->timing.samples_ms = s; c->timing.total_ms = t; c->timing.fallback_samples = nfix;
+        c->timing.dwell_ms = 0.f; c->timing.samples_ms = s; c->timing.total_ms = t; c->timing.fallback_samples = nfix;
         c->timing.carried_first_pass = b->carried_precount ? 1 : 0; c->timing.first_pass_ran_ahead = b->precounted ? 1 : 0;
     } else if (b->wait_rc) {
         c->err = "this batch failed on the device (see the first sqg_batch_wait)";
@@ -140,15 +136,15 @@ extern "C" int sqg_batch_compress(sqg_ctx_t* c, sqg_batch_t* b, sqg_svb_t* out) 
     if (n > 0) {
         if ((rc = ensure(c, (void**)&c->d_svb_size, &c->svb_size_cap, (size_t)n + 64, sizeof(long long)))) return rc;
         if ((rc = ensure(c, (void**)&c->d_svb_off, &c->svb_off_cap, (size_t)n + 64, sizeof(long long)))) return rc;
-        hipLaunchKernelGGL(k_svb_size, dim3((unsigned)n), dim3(256), 0, c->stream2, S.d_sig, S.d_sigoff, n, c->d_svb_size);
-        hipLaunchKernelGGL(k_svb_scan, dim3(1), dim3(1024), 0, c->stream2, c->d_svb_size, n, c->d_svb_off, h_dev);
+        hipLaunchKernelGGL(k_svb_size, dim3((unsigned)n), dim3(256), 0, c->stream, S.d_sig, S.d_sigoff, n, c->d_svb_size);
+        hipLaunchKernelGGL(k_svb_scan, dim3(1), dim3(1024), 0, c->stream, c->d_svb_size, n, c->d_svb_off, h_dev);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream2));           // the total sizes the output buffer
+        HIPCHK(c, hipStreamSynchronize(c->stream));           // the total sizes the output buffer
         const long long total = b->h_svboff[n];
         if ((rc = ensure(c, (void**)&c->d_svb, &c->svb_cap, (size_t)total + 64, 1))) return rc;
-        hipLaunchKernelGGL(k_svb_encode, dim3((unsigned)n), dim3(256), 0, c->stream2, S.d_sig, S.d_sigoff, n, c->d_svb_off, c->d_svb);
+        hipLaunchKernelGGL(k_svb_encode, dim3((unsigned)n), dim3(256), 0, c->stream, S.d_sig, S.d_sigoff, n, c->d_svb_off, c->d_svb);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream2));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     b->n_svb = b->h_svboff[n];
     b->compress_seq = ++c->compress_seq;

@@ -33,7 +33,7 @@ struct Run {                                                      // one sqg_bat
     sqg_ctx* c; sqg_batch* b; int phase; const uint32_t* before; const uint32_t* after;
     sqg_ctx::Slot* S; sqg_ctx::Slot* other; sqg_ctx::CountSet* Q;
     int n = 0, n_part = 0, dw = 0;
-    bool certified = false, inline_dwell = false, direct = false, fold = false, untimed = false, wave_links = false;
+    bool certified = false, direct = false, fold = false, untimed = false, wave_links = false;
     size_t n_pairs = 0, n_rows = 0;
     unsigned scan_wgs = 0, pgrid = 0;
     uint32_t *d_pcnt = nullptr, *slice_lo = nullptr, *slice_hi = nullptr, *pfirst = nullptr, *pstart = nullptr, *ptotal = nullptr;
@@ -89,7 +89,7 @@ static int run_buffers(Run& R) {
     R.n_rows = (size_t)c->nw * (size_t)c->num_kmer;
     R.scan_wgs = n > 0 ? (unsigned)((n + SCAN_WG - 1) / SCAN_WG) : 0u;
     if (phase != 2) {
-        // this slot's buffers were last used by the sample kernels of batch seq-2 (stream2)
+        // this slot's buffers were last used by the sample kernels and fix-ups of batch seq-2
         HIPCHK(c, hipStreamWaitEvent(c->stream, S.done, 0));
         if (b->ev_staged && hipEventQuery(b->ev_staged) != hipSuccess) HIPCHK(c, hipStreamWaitEvent(c->stream, b->ev_staged, 0));     // the batch's uploads and staging kernels (a barrier packet: not queued if they are done)
         b->other_fresh = other.reads_cap == 0 && n > 0;
@@ -101,7 +101,7 @@ static int run_buffers(Run& R) {
     // the pass writes is made large enough HERE (a reallocation must not happen between the kernels that advance the rows and the
     // hand-out); it is an optimisation: should a buffer not be had, the plain hand-out runs and the batch behind counts for itself.
     R.pre_nb = nullptr;
-    if (phase == 0 && n > 0 && b->n_chains > 0 && b->part && b->pieces && c->lds_ordered && c->use_dwell_stream && !SQG_DEV_ENV("SQG_SEPARATE_DWELL") &&
+    if (phase == 0 && n > 0 && b->n_chains > 0 && b->part && b->pieces && c->lds_ordered && c->use_dwell_stream &&
         !c->range_mode && !c->staged_q.empty() && !SQG_DEV_ENV("SQG_NO_PRECOUNT")) {
         sqg_batch* cand = c->staged_q.front();
         if (cand->seq > b->seq && cand->staged && !cand->ran && !cand->begun && !cand->precounted && cand->part && cand->pieces && cand->one == b->one &&
@@ -136,10 +136,8 @@ static void run_params(Run& R) {
     sqg_ctx* c = R.c; sqg_batch* b = R.b; const int phase = R.phase, n = R.n;
     sqg_ctx::Slot& S = *R.S; sqg_ctx::CountSet& Q = *R.Q;
     const sqg_profile_t& p = c->cfg.profile;
-    // Dwell draws are made inside k_events (SQG_SEPARATE_DWELL=1 keeps the stand-alone k_dwell for A/B runs).
-    R.inline_dwell = c->use_dwell_stream && !SQG_DEV_ENV("SQG_SEPARATE_DWELL");
     R.direct = c->num_kmer <= 4096;                             // the worker's whole row of stream states fits in LDS
-    R.dw = R.inline_dwell ? (R.certified && c->dwell_hi < 1.0e6 ? 1 : 2) : 0;
+    R.dw = c->use_dwell_stream ? (R.certified && c->dwell_hi < 1.0e6 ? 1 : 2) : 0;   // dwell draws are made inside the event kernels
     R.wave_links = b->pieces;                                   // (decided at staging: the links are then runs of pieces of reads)
     const int n_part = R.n_part;
     R.d_pcnt = c->d_pcnt[b->run_idx & 1];
@@ -182,9 +180,8 @@ static void run_params(Run& R) {
     P.slow_tiles = (R.certified && c->use_kmer_streams) ? S.d_slow : nullptr;
     // (round 5) bucketed hand-out, one launch sequence (no range sharding): the scan of the reads' totals runs as extra workgroups of
     // k_part_mid and the lean kernel's work items are prepared by extra workgroups of k_part_hist -- two launches and their gaps less per
-    // batch (36 us of a 3.6-ms step).  SQG_NO_FOLD=1 (development build) keeps the two kernels for A/B runs.
-    R.fold = phase == 0 && n > 0 && b->n_chains > 0 && b->part && !b->one && b->pieces && R.certified && c->use_kmer_streams &&
-             (c->lean_epl < 4 || SQG_LEAN_ITEMS4) && !SQG_DEV_ENV("SQG_MID_SPLIT") && !SQG_DEV_ENV("SQG_NO_FOLD");
+    // batch (36 us of a 3.6-ms step).
+    R.fold = phase == 0 && n > 0 && b->n_chains > 0 && b->part && !b->one && b->pieces && R.certified && c->use_kmer_streams;
     memset(&R.SA, 0, sizeof R.SA);
     if (n > 0 && phase != 1) {
         // the scan also writes the offsets through the batch's pinned host mapping (no copy between kernels)
@@ -288,7 +285,7 @@ static void launch_rows_advance(Run& R) {
     else hipLaunchKernelGGL(k_rows_advance<false>, ag, dim3(256), 0, c->stream, c->d_rows, c->d_pow, R.n_rows, R.before, c->d_xcounts, R.after);
 }
 
-// ---- in front of every regime: the rows' counts kept in range, the timing event, dwells that are not drawn inside the event kernels ----
+// ---- in front of every regime: the rows' counts kept in range, the timing event, the totals of constant dwells ----
 static void plan_first_pass(Run& R, RunPlan& plan) {
     sqg_ctx* c = R.c; sqg_batch* b = R.b; const int n = R.n;
     if (R.phase == 2) return;
@@ -309,27 +306,10 @@ static void plan_first_pass(Run& R, RunPlan& plan) {
         c->row_bound += bnd;
     }
     if (!R.untimed) plan.push_back({"event: start", [&R]() -> int { HIPCHK(R.c, hipEventRecord(R.b->ev[0], R.c->stream)); return SQG_OK; }});
-    if (n > 0 && c->use_dwell_stream && !R.inline_dwell)
-        plan.push_back({"k_dwell", [&R]() -> int {
-            sqg_ctx* c = R.c; sqg_batch* b = R.b; const sqg_profile_t& p = c->cfg.profile;
-            HIPCHK(c, hipMemsetAsync(R.Q->d_seglen, 0, (size_t)2 * R.n * sizeof(unsigned long long), c->stream));
-            const long long nblk = (b->n_events + DW_EPB - 1) / DW_EPB;
-            if (nblk > 0) {
-                if (R.certified)
-                    hipLaunchKernelGGL(k_dwell<1>, dim3((unsigned)nblk), dim3(256), 0, c->stream, b->d_reads, R.n, b->d_blk_read,
-                                       b->n_events, c->d_pow, p.dwell_mean, p.dwell_std, c->delta_x, R.Q->d_dwell, R.Q->d_seglen, b->d_err);
-                else
-                    hipLaunchKernelGGL(k_dwell<0>, dim3((unsigned)nblk), dim3(256), 0, c->stream, b->d_reads, R.n, b->d_blk_read,
-                                       b->n_events, c->d_pow, p.dwell_mean, p.dwell_std, 0.f, R.Q->d_dwell, R.Q->d_seglen, b->d_err);
-            }
-            return SQG_OK; }});
-    else if (n > 0 && !c->use_dwell_stream)
+    if (n > 0 && !c->use_dwell_stream)
         plan.push_back({"upload: constant dwells' totals", [&R]() -> int {
             HIPCHK(R.c, hipMemcpyAsync(R.Q->d_seglen, R.b->seglen_host.data(), (size_t)2 * R.n * sizeof(unsigned long long), hipMemcpyHostToDevice, R.c->stream));
             return SQG_OK; }});
-    b->dwell_timed = c->use_dwell_stream && !R.inline_dwell && !R.untimed;        // stand-alone k_dwell (A/B runs): two more timing events
-    if (b->dwell_timed)
-        plan.push_back({"events: dwell kernel done", [&R]() -> int { HIPCHK(R.c, hipEventRecord(R.b->ev[1], R.c->stream)); HIPCHK(R.c, hipEventRecord(R.b->ev[2], R.c->stream)); return SQG_OK; }});
 }
 
 // ---- few workers, the hand-out over events bucketed by the top bits of the rank (k_part.h); one partition for k <= 6 ---------------------
@@ -346,8 +326,7 @@ static void plan_bucketed(Run& R, RunPlan& plan) {
                 if (b->split_reads && R.dw) Q.seglen_dirty = (size_t)R.n;   // (until this batch's k_fixup is queued: a run that fails half-way leaves them dirty)
                 launch_part_events(R, R.dw, true);
                 return SQG_OK; }});
-        const bool mid_split = SQG_DEV_ENV("SQG_MID_SPLIT") != nullptr;   // A/B: the four small kernels between the passes, one by one
-        if (b->split_reads && (b->one || mid_split))
+        if (b->split_reads && b->one)
             plan.push_back({"k_part_tile_bases", [&R]() -> int { hipLaunchKernelGGL(k_part_tile_bases, dim3((unsigned)R.b->n_pieces), dim3(64), 0, R.c->stream, R.P); return SQG_OK; }});
         if (b->one) {
             // one partition: the pass above has written part[] in chain order; the slices of every worker chain's events
@@ -355,24 +334,15 @@ static void plan_bucketed(Run& R, RunPlan& plan) {
                 hipLaunchKernelGGL(k_part_slices, dim3(1), dim3(1024), 0, R.c->stream, R.pstart, R.b->d_wchain_total, (int)R.n_pairs, R.b->slice_len, R.pfirst, R.slice_lo, R.slice_hi);
                 return SQG_OK; }});
         } else {
-            if (mid_split)
-                plan.push_back({"k_part_offsets + k_part_slices + k_part_slice_bounds", [&R]() -> int {
-                    sqg_ctx* c = R.c; sqg_batch* b = R.b;
-                    hipLaunchKernelGGL(k_part_offsets, dim3((unsigned)R.n_part, (unsigned)b->n_wchains), dim3(1024), 0, c->stream, R.d_pcnt,
-                                       R.d_pcnt + (size_t)b->n_chains * R.n_part, R.n_part, b->n_chains, b->d_wlink_off, R.ptotal);
-                    hipLaunchKernelGGL(k_part_slices, dim3(1), dim3(1024), 0, c->stream, R.pstart, R.ptotal, (int)R.n_pairs, b->slice_len, R.pfirst, nullptr, nullptr);
-                    hipLaunchKernelGGL(k_part_slice_bounds, dim3((R.pgrid + 255) / 256), dim3(256), 0, c->stream, R.pstart, R.ptotal, (int)R.n_pairs, b->slice_len, R.pfirst, R.slice_lo, R.slice_hi);
-                    return SQG_OK; }});
-            else
-                // offsets per (partition, worker chain), the tile offsets of split reads, the slices and their bounds -- and (fold) the scan of
-                // the reads' totals: one launch
-                plan.push_back({R.fold ? "k_part_mid (+ the scan)" : "k_part_mid", [&R]() -> int {
-                    sqg_ctx* c = R.c; sqg_batch* b = R.b;
-                    const int n_off = (int)R.n_pairs, n_pc = b->split_reads ? b->n_pieces : 0, n_sc = R.fold ? (int)R.scan_wgs : 0;
-                    hipLaunchKernelGGL(k_part_mid, dim3((unsigned)(n_off + (n_pc + 15) / 16 + n_sc)), dim3(1024), 0, c->stream, R.P, R.d_pcnt,
-                                       R.d_pcnt + (size_t)b->n_chains * R.n_part, R.n_part, b->n_chains, b->d_wlink_off, R.ptotal, R.pstart, (int)R.n_pairs, b->slice_len,
-                                       R.pfirst, R.slice_lo, R.slice_hi, n_off, n_pc, c->d_mid_done, R.SA, n_sc);
-                    return SQG_OK; }});
+            // offsets per (partition, worker chain), the tile offsets of split reads, the slices and their bounds -- and (fold) the scan of
+            // the reads' totals: one launch
+            plan.push_back({R.fold ? "k_part_mid (+ the scan)" : "k_part_mid", [&R]() -> int {
+                sqg_ctx* c = R.c; sqg_batch* b = R.b;
+                const int n_off = (int)R.n_pairs, n_pc = b->split_reads ? b->n_pieces : 0, n_sc = R.fold ? (int)R.scan_wgs : 0;
+                hipLaunchKernelGGL(k_part_mid, dim3((unsigned)(n_off + (n_pc + 15) / 16 + n_sc)), dim3(1024), 0, c->stream, R.P, R.d_pcnt,
+                                   R.d_pcnt + (size_t)b->n_chains * R.n_part, R.n_part, b->n_chains, b->d_wlink_off, R.ptotal, R.pstart, (int)R.n_pairs, b->slice_len,
+                                   R.pfirst, R.slice_lo, R.slice_hi, n_off, n_pc, c->d_mid_done, R.SA, n_sc);
+                return SQG_OK; }});
             plan.push_back({"k_part_events<scatter>: every event to its slot", [&R]() -> int {             // (the dwell is in memory now)
                 const int left = R.c->cal_runs_left;
                 int rc = place_calibrate(R); if (rc) return rc;
@@ -401,9 +371,8 @@ static void plan_bucketed(Run& R, RunPlan& plan) {
         const dim3 pg((unsigned)((c->num_kmer + 63) / 64), (unsigned)b->n_wchains);
 #define SCANL(R_, G_) hipLaunchKernelGGL((k_part_scan<R_, G_>), dim3((unsigned)((c->num_kmer + R_ - 1) / R_), (unsigned)b->n_wchains), dim3(R_ * G_), 0, c->stream, \
                                         c->d_phist, c->d_rows, c->num_kmer, R.n_part, R.pfirst, b->d_wlink_worker, R.before, c->d_pow, R.P.seed_base, R.P.seed_step, R.direct ? 1 : 0, b->d_err)
-        const int scan_g4 = dev_env_int(SQG_DEV_ENV("SQG_SCAN_G4"), 32);   // A/B knob
         if ((long long)b->max_slices <= 8 * (long long)R.n_pairs) SCANL(256, 1);       // a slice or two per pair: one thread per rank walks them
-        else if ((long long)b->max_slices <= scan_g4 * (long long)R.n_pairs && (size_t)pg.x * pg.y >= 512) SCANL(64, 4);   // a dozen (small batches): 16 runs would be 16 x the wavefronts, most of them idle
+        else if ((long long)b->max_slices <= 32 * (long long)R.n_pairs && (size_t)pg.x * pg.y >= 512) SCANL(64, 4);   // a dozen (small batches): 16 runs would be 16 x the wavefronts, most of them idle
         else if ((size_t)pg.x * pg.y >= 512) SCANL(64, 16);
         else SCANL(16, 64);
 #undef SCANL
@@ -431,26 +400,13 @@ static void plan_bucketed(Run& R, RunPlan& plan) {
             memset(&Pn, 0, sizeof Pn);
             count_params(c, nb, NQ, R.n_part, c->d_pcnt[(b->run_idx + 1) & 1], Pn);
             if (nb->one) { Pn.one = 1; Pn.part = other.d_part; Pn.poff = nb->d_link_slot; }
-            const dim3 fg((unsigned)(dev_env_int(SQG_DEV_ENV("SQG_PHC_GRID"), 4) * c->num_cu)), ft(64 * (1 + PHC_COUNT_WAVES));   // (A/B: workgroups per CU)
-            // (development build, timing experiments: 1 -- the fused launch hands out only, the next batch's pass follows as a launch
-            // of its own; 2 -- the plain hand-out first, the fused launch counts only)
-            const int phc_abl = dev_env_int(SQG_DEV_ENV("SQG_PHC_ABL"), 0);
+            const dim3 fg((unsigned)(4 * c->num_cu)), ft(64 * (1 + PHC_COUNT_WAVES));   // (workgroups per CU)
             const int dw = R.dw;
-            if (phc_abl == 2) hipLaunchKernelGGL(k_part_hand_ord, dim3(R.pgrid), dim3(64), 0, c->stream, S.d_part, S.d_part_state, R.slice_lo, R.slice_hi, R.pfirst + R.n_pairs, c->d_phist, c->d_pow, b->d_err, order_fault);
-            const uint32_t* const ns_ptr = phc_abl == 2 ? c->d_zero : R.pfirst + R.n_pairs;
-            const int nl_fused = phc_abl == 1 ? 0 : nb->n_chains;
-#define PHCL(D_, M_) hipLaunchKernelGGL((k_part_hand_count<D_, M_>), fg, ft, 0, c->stream, S.d_part, S.d_part_state, R.slice_lo, R.slice_hi, ns_ptr, c->d_phist, c->d_pow, \
-                                    b->d_err, order_fault, Pn, nl_fused, (uint32_t)nb->n_events, c->num_cu)
+#define PHCL(D_, M_) hipLaunchKernelGGL((k_part_hand_count<D_, M_>), fg, ft, 0, c->stream, S.d_part, S.d_part_state, R.slice_lo, R.slice_hi, R.pfirst + R.n_pairs, c->d_phist, c->d_pow, \
+                                    b->d_err, order_fault, Pn, nb->n_chains, (uint32_t)nb->n_events, c->num_cu)
             if (nb->one) { if (dw == 1) PHCL(1, PEV_ONE); else PHCL(2, PEV_ONE); }
             else { if (dw == 1) PHCL(1, PEV_COUNT); else PHCL(2, PEV_COUNT); }
 #undef PHCL
-            if (phc_abl == 1) {
-                const dim3 g1((unsigned)((nb->n_chains + PEV_WAVES - 1) / PEV_WAVES)), t1(64 * PEV_WAVES);
-                if (nb->one) { if (dw == 1) hipLaunchKernelGGL((k_part_events<1, PEV_ONE>), g1, t1, 0, c->stream, Pn, nb->n_chains, (uint32_t)nb->n_events);
-                               else hipLaunchKernelGGL((k_part_events<2, PEV_ONE>), g1, t1, 0, c->stream, Pn, nb->n_chains, (uint32_t)nb->n_events); }
-                else if (dw == 1) hipLaunchKernelGGL((k_part_events<1, PEV_COUNT>), g1, t1, 0, c->stream, Pn, nb->n_chains, (uint32_t)nb->n_events);
-                else hipLaunchKernelGGL((k_part_events<2, PEV_COUNT>), g1, t1, 0, c->stream, Pn, nb->n_chains, (uint32_t)nb->n_events);
-            }
             nb->precounted = true; nb->cset = ncs; nb->cset_gen = ++NQ.gen; nb->pre_slot = b->slot ^ 1;
             b->carried_precount = true;                           // (sqg_get_timing: this batch's event side holds the successor's first pass)
             return SQG_OK; }});
@@ -505,11 +461,8 @@ static void plan_chains(Run& R, RunPlan& plan) {
 static int plan_samples(Run& R, RunPlan& plan) {
     sqg_ctx* c = R.c; sqg_batch* b = R.b; const int n = R.n;
     sqg_ctx::Slot& S = *R.S; sqg_ctx::CountSet& Q = *R.Q; SigParams& P = R.P;
-    R.tail = c->stream2;
+    R.tail = c->stream;
     R.seglen_zeroed = false;
-    auto split_streams = [&R]() -> int {                          // event side done: the sample kernels may start on their own stream (SQG_OVERLAP), next to the next batch's event side
-        if (R.c->stream2 != R.c->stream) { HIPCHK(R.c, hipEventRecord(R.b->ev[7], R.c->stream)); HIPCHK(R.c, hipStreamWaitEvent(R.c->stream2, R.b->ev[7], 0)); }
-        return SQG_OK; };
     if (n > 0 && b->n_chains > 0) {
         P.sig = S.d_sig; P.fix = S.d_fix; P.fix_count = S.d_fix_count;
         P.fix_sh = S.d_fix_sh; P.fix_sh_cap = S.fix_sh_per; P.fix_sh_count = S.d_fix_sh_count; P.fix_sh_stat = S.d_fix_count + 4; P.host_res = reinterpret_cast<unsigned int*>(b->h_sigoff_dev + (b->h_n - SQG_HRES_LL)); P.fix_tag = (int)(++c->fix_tickets & 0x3fffffffull) + 1;   // (a tag per launch, also when a batch is run again after a failed run: stale entries of the first attempt must not match)
@@ -521,35 +474,26 @@ static int plan_samples(Run& R, RunPlan& plan) {
             fprintf(stderr, "[sqg] batch %lld: %d reads, %lld events, %d links in %d worker chains, %d pieces, %lld slices of %u events at most%s\n", (long long)b->run_idx, n, (long long)b->n_events,
                     b->n_chains, b->n_wchains, b->n_pieces, (long long)b->max_slices, b->slice_len, b->precounted ? "; first event pass: ran ahead, with the previous batch's hand-out" : "");
         if (R.certified && c->use_kmer_streams) {
-            // work items of 256 events (4 per lane) look their descriptor up themselves, on the scalar unit, unless k_items prepared them;
-            // with shorter items (profiles with long dwells) the look-up chain per item is always worth the kernel
-            if (R.fold) {}                                        // (the work items were prepared inside k_part_hist)
-            else if (c->lean_epl < 4 || SQG_LEAN_ITEMS4)
+            if (!R.fold)                                          // (else the work items were prepared inside k_part_hist)
                 plan.push_back({"k_items", [&R]() -> int { const int ns = (int)R.b->n_stiles; hipLaunchKernelGGL(k_items, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, R.c->stream, R.P, ns); return SQG_OK; }});
-            else P.items = nullptr;
-            plan.push_back({"k_samples_lean", [&R, split_streams]() -> int {
+            plan.push_back({"k_samples_lean", [&R]() -> int {
                 sqg_ctx* c = R.c; sqg_batch* b = R.b; const SigParams& P = R.P;
-                int rs = split_streams(); if (rs) return rs;
                 const int n_stiles = (int)b->n_stiles;
-                unsigned lgrid = (unsigned)((n_stiles + 3) / 4);
-                const int lean_grid_cap = dev_env_int(SQG_DEV_ENV("SQG_LEAN_GRID"), 0);   // A/B knob
-                if (lean_grid_cap > 0) lgrid = std::min(lgrid, (unsigned)lean_grid_cap);
-                if (!R.untimed) HIPCHK(c, hipEventRecord(b->ev[5], c->stream2));
-                const unsigned lean_dynlds = (unsigned)dev_env_int(SQG_DEV_ENV("SQG_LEAN_DYNLDS"), 0);   // A/B: bytes of LDS a workgroup reserves on top (fewer workgroups per CU)
-#define LEANL(R_, E_) hipLaunchKernelGGL((k_samples_lean<R_, E_>), dim3(lgrid), dim3(256), lean_dynlds, c->stream2, P, n_stiles)
+                const unsigned lgrid = (unsigned)((n_stiles + 3) / 4);
+                if (!R.untimed) HIPCHK(c, hipEventRecord(b->ev[5], c->stream));
+#define LEANL(R_, E_) hipLaunchKernelGGL((k_samples_lean<R_, E_>), dim3(lgrid), dim3(256), 0, c->stream, P, n_stiles)
                 if (P.rna) { if (c->lean_epl == 4) LEANL(true, 4); else if (c->lean_epl == 2) LEANL(true, 2); else LEANL(true, 1); }
                 else { if (c->lean_epl == 4) LEANL(false, 4); else if (c->lean_epl == 2) LEANL(false, 2); else LEANL(false, 1); }
 #undef LEANL
-                if (!R.untimed) HIPCHK(c, hipEventRecord(b->ev[6], c->stream2));
+                if (!R.untimed) HIPCHK(c, hipEventRecord(b->ev[6], c->stream));
                 b->lean_timed = !R.untimed;
                 return SQG_OK; }});
             // what is left -- the items the lean kernel did not take (usually none) and the FP64 fix-ups, small latency-bound
             // kernels -- goes to a stream of its own: the next batch's event side does not wait for it
             plan.push_back({"k_samples<generic> + k_fixup (their own stream)", [&R]() -> int {
                 sqg_ctx* c = R.c; sqg_batch* b = R.b; SigParams& P = R.P;
-                const bool fix_inline = SQG_DEV_ENV("SQG_FIX_INLINE") != nullptr;   // A/B: the left-over kernels on the batch's own stream
-                HIPCHK(c, hipEventRecord(R.S->sampled, c->stream2));
-                if (!fix_inline) { HIPCHK(c, hipStreamWaitEvent(c->fix_stream, R.S->sampled, 0)); R.tail = c->fix_stream; }
+                HIPCHK(c, hipEventRecord(R.S->sampled, c->stream));
+                HIPCHK(c, hipStreamWaitEvent(c->fix_stream, R.S->sampled, 0)); R.tail = c->fix_stream;
                 if (SQG_DEV_ENV("SQG_ABL_NOFIX")) return SQG_OK;  // timing-only ablation (results are wrong): what the left-over kernels cost the step
                 const int n_tiles = (int)b->n_tiles;
                 const unsigned sgrid = (unsigned)((n_tiles + 3) / 4);
@@ -560,15 +504,14 @@ static int plan_samples(Run& R, RunPlan& plan) {
                 b->fixup_launched = true;                         // (its per-list statistics words are this batch's)
                 return SQG_OK; }});
         } else {
-            plan.push_back({"k_samples<generic>", [&R, split_streams]() -> int {
+            plan.push_back({"k_samples<generic>", [&R]() -> int {
                 sqg_ctx* c = R.c; const int n_tiles = (int)R.b->n_tiles;
-                int rs = split_streams(); if (rs) return rs;
                 const unsigned sgrid = (unsigned)((n_tiles + 3) / 4);
-                if (R.certified) hipLaunchKernelGGL((k_samples<1, true>), dim3(sgrid), dim3(256), 0, c->stream2, R.P, n_tiles);
-                else hipLaunchKernelGGL((k_samples<0, true>), dim3(sgrid), dim3(256), 0, c->stream2, R.P, n_tiles);
+                if (R.certified) hipLaunchKernelGGL((k_samples<1, true>), dim3(sgrid), dim3(256), 0, c->stream, R.P, n_tiles);
+                else hipLaunchKernelGGL((k_samples<0, true>), dim3(sgrid), dim3(256), 0, c->stream, R.P, n_tiles);
                 return SQG_OK; }});
         }
-    } else plan.push_back({"streams: event side done", split_streams});
+    }
     return SQG_OK;
 }
 

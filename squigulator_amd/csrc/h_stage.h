@@ -51,14 +51,14 @@ static int grow_slot(sqg_ctx* c, sqg_ctx::Slot& Z, const sqg_batch* b, bool with
     const int n = b->n;
     const bool certified = c->cfg.mode == SQG_MODE_CERTIFIED;
     if ((size_t)n + 1 > Z.reads_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream2));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         (void)hipFree(Z.d_sigoff); Z.d_sigoff = nullptr;
         const size_t cap = (size_t)n + 1 + (size_t)n / 2;
         HIPCHK(c, hipMalloc(&Z.d_sigoff, cap * sizeof(long long)));
         Z.reads_cap = cap;
     }
     if (Z.cal_prev && (size_t)b->n_events + 64 > Z.evrec_cap) {    // (the event records grow: a placement candidate's predecessor is not coming back)
-        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream2)); HIPCHK(c, hipStreamSynchronize(c->fix_stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->fix_stream));
         (void)hipFree(Z.cal_prev); Z.cal_prev = nullptr; Z.cal_pending = false;
     }
     if ((rc2 = ensure(c, (void**)&Z.d_evrec, &Z.evrec_cap, (size_t)b->n_events + 64, sizeof(uint2)))) return rc2;
@@ -67,11 +67,7 @@ static int grow_slot(sqg_ctx* c, sqg_ctx::Slot& Z, const sqg_batch* b, bool with
         if ((rc2 = ensure(c, (void**)&Z.d_lbase, &Z.lbase_cap, (size_t)b->n_chains * PART_MAX, sizeof(uint32_t)))) return rc2;
         if ((rc2 = ensure(c, (void**)&Z.d_tile_link, &Z.tile_link_cap, (size_t)b->n_tiles + 64, sizeof(int)))) return rc2;
     }
-#if defined(SQG_ABL_HANDOVER)
-    if (b->part && (rc2 = ensure(c, (void**)&Z.d_part_state, &Z.part_state_cap, (size_t)4 * ((size_t)b->n_events + PART_SLACK), sizeof(uint32_t)))) return rc2;
-#else
     if (b->part && (rc2 = ensure(c, (void**)&Z.d_part_state, &Z.part_state_cap, (size_t)b->n_events + PART_SLACK, sizeof(uint32_t)))) return rc2;
-#endif
     if ((rc2 = ensure(c, (void**)&Z.d_slow, &Z.slow_cap, (size_t)b->n_tiles + 64, sizeof(int)))) return rc2;
     if (certified && c->use_kmer_streams) {
         if ((rc2 = ensure(c, (void**)&Z.d_items, &Z.items_cap, (size_t)b->n_stiles + 64, sizeof(ItemDesc)))) return rc2;
@@ -117,7 +113,6 @@ struct Staging {
     std::vector<int> chain_order;
     // draws(): the workers' scalar streams as they stood (a staging that fails afterwards puts them back: bail())
     std::vector<uint32_t> snap_time; std::vector<long long> snap_off, snap_med;
-    std::vector<int> blk_read;                                   // dwell_blocks()
 
     Staging(sqg_ctx* c_, int n_, const char* seqs_, const int64_t* seq_off_, const int32_t* worker_, const SampleRec* d_rec_, const uint32_t* d_mstate_)
         : c(c_), n(n_), seqs(seqs_), seq_off(seq_off_), worker(worker_), d_rec(d_rec_), d_mstate(d_mstate_), p(c_->cfg.profile),
@@ -248,7 +243,6 @@ struct Staging {
                 if (!part_ok) target = std::min<long long>(target, std::max<long long>(8, (long long)(((size_t)1 << 30) / row_bytes)));
                 std::vector<int> link_off(1, 0);
                 b->pieces = wave_links;
-                const bool whole_links = !SQG_DEV_ENV("SQG_NO_WHOLE_LINKS");           // A/B (development library)
                 for (int q = 0; q < n_wchains && wave_links; q++) {
                     // a link of k_part_events is a run of PIECES: whole reads, and the pieces (whole 512-event segments) of reads longer
                     // than a link should be -- one wavefront walks a link, and a read of 10^5 events would keep it busy ten times as
@@ -269,7 +263,7 @@ struct Staging {
                         if (ne <= per + per / 4 || ne <= PEV_SEG) {
                             pieces.push_back(Piece{r, 0, (int)ne, 0});
                             if ((acc += ne) >= per) close();
-                        } else if (whole_links && per == per_cap && ne < (1 << EVR_REL_BITS) - PEV_SEG) {
+                        } else if (per == per_cap && ne < (1 << EVR_REL_BITS) - PEV_SEG) {
                             // a large batch -- the cap above, not the link target, sets `per` -- and a read that is longer than that but fits a link:
                             // a link of its own, whole (round 5: at the headline size every 10-kb read, 9992 events, was cut into 7168 + 2824: twice the
                             // links, half of them short, and the cut reads' tile offsets patched by k_part_tile_bases).  A small batch keeps cutting:
@@ -496,31 +490,17 @@ struct Staging {
         }
     }
 
-    // ---- dwell kernel launch geometry: first read of every DW_EPB-event block
-    void dwell_blocks() {
-        const long long nblk = (nev + DW_EPB - 1) / DW_EPB;
-        blk_read.assign((size_t)std::max<long long>(nblk, 1), 0);
-        {
-            int r = 0;
-            for (long long bi = 0; bi < nblk; bi++) {
-                const long long g = bi * DW_EPB;
-                while (r + 1 < n && g >= rd[(size_t)r + 1].ev_off) r++;
-                blk_read[(size_t)bi] = r;
-            }
-        }
-    }
-
     // ---- the batch's device block, the uploads, the staging kernels
     int upload() {
 #define CHKB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { c->err = std::string(#call) + ": " + hipGetErrorString(e_); return bail(e_ == hipErrorOutOfMemory ? SQG_ENOMEM : SQG_EDEVICE); } } while (0)
-        size_t meta_bytes = 0, mo_err = 0, mo_reads = 0, mo_blk = 0, mo_coff = 0, mo_crd = 0, mo_ord = 0, mo_wlo = 0, mo_wlw = 0, mo_cb = 0, mo_ls = 0, mo_wt = 0, mo_pc = 0;
+        size_t meta_bytes = 0, mo_err = 0, mo_reads = 0, mo_coff = 0, mo_crd = 0, mo_ord = 0, mo_wlo = 0, mo_wlw = 0, mo_cb = 0, mo_ls = 0, mo_wt = 0, mo_pc = 0;
         {   // one device allocation per batch, carved into the batch's arrays (256-byte aligned)
             size_t off = 0;
             auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
             // the host-built arrays first and back to back: they go up in one copy from the batch's pinned mirror
             const size_t o_err = carve(256),
                          o_reads = carve(std::max<size_t>(1, rd.size()) * sizeof(ReadDesc)),
-                         o_blk = carve(blk_read.size() * sizeof(int)), o_coff = carve(chain_off.size() * sizeof(int)),
+                         o_coff = carve(chain_off.size() * sizeof(int)),
                          o_crd = carve(std::max<size_t>(1, chain_reads.size()) * sizeof(int)),
                          o_ord = carve(std::max<size_t>(1, chain_order.size()) * sizeof(int)),
                          o_wlo = carve(wlink_off.size() * sizeof(int)), o_wlw = carve(std::max<size_t>(1, wlink_worker.size()) * sizeof(int)),
@@ -531,7 +511,7 @@ struct Staging {
             const size_t o_ptot = carve(std::max<size_t>(1, pieces.size()) * sizeof(uint32_t));
             const size_t o_bases = carve((size_t)nb + 1024),        // (k_part_events reads a whole segment + halo from a read's last segment on)
                          o_st = carve((size_t)std::max<long long>(nst, 1) * sizeof(int)), o_t = carve((size_t)std::max<long long>(ntile, 1) * sizeof(int));
-            mo_err = o_err; mo_reads = o_reads; mo_blk = o_blk; mo_coff = o_coff; mo_crd = o_crd; mo_ord = o_ord; mo_wlo = o_wlo; mo_wlw = o_wlw; mo_cb = o_cb; mo_ls = o_ls; mo_wt = o_wt; mo_pc = o_pc;
+            mo_err = o_err; mo_reads = o_reads; mo_coff = o_coff; mo_crd = o_crd; mo_ord = o_ord; mo_wlo = o_wlo; mo_wlw = o_wlw; mo_cb = o_cb; mo_ls = o_ls; mo_wt = o_wt; mo_pc = o_pc;
             // a freed batch's block, pinned offsets and events are reused when they are large enough
             for (size_t pi = 0; pi < c->pool.size(); pi++) {
                 sqg_ctx::Recycled& r = c->pool[pi];
@@ -557,7 +537,7 @@ struct Staging {
             }
             uint8_t* base = b->d_block;
             b->d_err = (unsigned int*)(base + o_err);
-            b->d_bases = base + o_bases; b->d_reads = (ReadDesc*)(base + o_reads); b->d_blk_read = (int*)(base + o_blk);
+            b->d_bases = base + o_bases; b->d_reads = (ReadDesc*)(base + o_reads);
             b->d_chain_off = (int*)(base + o_coff); b->d_chain_reads = (int*)(base + o_crd); b->d_stile_read = (int*)(base + o_st);
             b->d_tile_read = (int*)(base + o_t); b->d_chain_order = (int*)(base + o_ord);
             b->d_wlink_off = (int*)(base + o_wlo); b->d_wlink_worker = (int*)(base + o_wlw);
@@ -568,7 +548,6 @@ struct Staging {
             uint8_t* m = b->h_meta;
             memset(m + mo_err, 0, 256);                         // the batch's error word starts clear
             if (n) memcpy(m + mo_reads, rd.data(), rd.size() * sizeof(ReadDesc));
-            memcpy(m + mo_blk, blk_read.data(), blk_read.size() * sizeof(int));
             memcpy(m + mo_coff, chain_off.data(), chain_off.size() * sizeof(int));
             if (n) memcpy(m + mo_crd, chain_reads.data(), chain_reads.size() * sizeof(int));
             if (b->n_chains) memcpy(m + mo_ord, chain_order.data(), chain_order.size() * sizeof(int));
@@ -642,7 +621,6 @@ static int stage_common(sqg_ctx_t* c, int32_t n, const char* seqs, const int64_t
     s.launch_order();
     s.draws();
     st_mark("per-read draws");
-    s.dwell_blocks();
     st_mark("chains+streams+blocks");
     if ((rc = s.upload())) return rc;
     st_mark("mallocs+enqueue");

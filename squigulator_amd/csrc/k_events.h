@@ -1,4 +1,4 @@
-// k_events.h -- k_init_rows, k_dwell, k_scan and k_events: dwell draws, k-mer ranks, in-order hand-out of the k-mer streams
+// k_events.h -- k_init_rows, k_scan and k_events: dwell draws, k-mer ranks, in-order hand-out of the k-mer streams
 // Part of the device code of the per-read signal path; included through sqg_kernels.h (see there for the overview).
 #pragma once
 
@@ -23,92 +23,6 @@ __global__ __launch_bounds__(64) void k_fill_tiles(const ReadDesc* __restrict__ 
     const int nt = (ne + 63) >> 6, nst = (ne + lean_ev - 1) / lean_ev;
     for (int t = threadIdx.x; t < nt; t += 64) tile_read[rd.tile_off + t] = r;
     for (int t = threadIdx.x; t < nst; t += 64) stile_read[rd.stile_off + t] = r;
-}
-
-// ---- k_dwell: one thread per event of the batch --------------------------------------------
-// sps = round(nrng(rand_time)); sps = sps<1 ? -sps+1 : sps           (src/gensig.c:255-256)
-// Event e of a read uses draws 2e+1, 2e+2 after the worker's time-stream state at the start of
-// the read: position addressed by the jump a^(2e) (two LDS table levels, a third in memory).
-#define DW_RD 16           // read descriptors cached per block (reads are >= ~190 events)
-#define DW_IT 8            // events per thread: the block's fixed latencies (tables, descriptors) are paid once per 2048 events
-#define DW_EPB (256 * DW_IT)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_dwell(const ReadDesc* __restrict__ reads, int n_reads,
-                                               const int* __restrict__ blk_read, long long n_events,
-                                               const uint32_t* __restrict__ pw, double dmean, double dstd,
-                                               float delta_x,
-                                               uint16_t* __restrict__ dwell,
-                                               unsigned long long* __restrict__ seglen,
-                                               unsigned int* __restrict__ err) {
-    __shared__ uint32_t j0[POW_N], j1[POW_N];          // a^(2j), a^(2*1024*j)
-    __shared__ long long r_ev[DW_RD + 1];
-    __shared__ uint32_t r_c0[DW_RD];
-    __shared__ int r_ne0[DW_RD];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < POW_N; i += 256) { j0[i] = pw[2 * POW_N + i]; j1[i] = pw[3 * POW_N + i]; }
-    const int rb = blk_read[blockIdx.x];
-    if (tid <= DW_RD) {
-        const int q = rb + tid;
-        r_ev[tid] = q < n_reads ? reads[q].ev_off : 0x7fffffffffffffffLL;
-        if (tid < DW_RD && q < n_reads) { r_c0[tid] = reads[q].time_c0; r_ne0[tid] = reads[q].ne0; }
-    }
-    __syncthreads();
-    const float sf = (float)dstd, mf = (float)dmean;
-    const float mag = fabsf(mf) + 7.0f * fabsf(sf) + 1.0f;
-    // delta_x*s (swept) + float roundings of s, m, the fma and the +1/2 (each <= 2^-24 * mag) + slack
-    const float eps = delta_x * fabsf(sf) + 4.0f * 5.9604645e-8f * mag + 1e-6f;
-    int q = 0;                                          // cached descriptor index (monotone over the iterations)
-    for (int it = 0; it < DW_IT; it++) {
-        const long long gid = (long long)blockIdx.x * DW_EPB + it * 256 + tid;
-        const bool valid = gid < n_events;
-        int r = rb, sps = 0, seg = 0;
-        if (valid) {
-            while (q + 1 < DW_RD && gid >= r_ev[q + 1]) q++;
-            uint32_t e, c0; int ne0;
-            if (gid < r_ev[q + 1]) { e = (uint32_t)(gid - r_ev[q]); c0 = r_c0[q]; ne0 = r_ne0[q]; r = rb + q; }
-            else {                                     // more than DW_RD reads in one block: walk the table
-                r = rb + q;
-                while (r + 1 < n_reads && gid >= reads[r + 1].ev_off) r++;
-                e = (uint32_t)(gid - reads[r].ev_off); c0 = reads[r].time_c0; ne0 = reads[r].ne0;
-            }
-            uint32_t jp = j0[e & (POW_N - 1)];
-            const uint32_t hi = (e >> 10) & (POW_N - 1), hi2 = e >> 20;
-            if (hi) jp = lcg_mul(jp, j1[hi]);
-            if (hi2) jp = lcg_mul(jp, pw[4 * POW_N + hi2]);
-            const uint32_t c1 = lcg_mul(lcg_mul(c0, jp), LCG_A);
-            bool decided = false;
-            if (MODE == 1) {
-                // v' = x'*s + m in fp32; round(v) = floor(v+1/2) unless v is within eps of a half-integer
-                const float x = box_muller_fast(c1);
-                const float g = __builtin_fmaf(x, sf, mf) + 0.5f;
-                const float fl = floorf(g);
-                const float fr = g - fl;
-                if (fabsf(fr - 0.5f) < 0.5f - eps && c1 <= LCG_M - (1u << NEAR_ONE_BITS) && fabsf(g) < 1.0e6f) {
-                    sps = (int)fl;
-                    decided = true;
-                }
-            }
-            if (!decided) {
-                const double z = box_muller_exact(c1, lcg_mul(c1, LCG_A));
-                const double v = (z * dstd) + dmean;                 // nrng: (x * s) + m
-                sps = (int)round(v);                                 // src/gensig.c:255
-            }
-            sps = sps < 1 ? -sps + 1 : sps;                          // src/gensig.c:256
-            if (sps > 65535) { atomicOr(err, 1u); sps = 65535; }
-            dwell[gid] = (uint16_t)sps;
-            seg = e >= (uint32_t)ne0;
-        }
-        // per-read totals: one atomic per wavefront when the wave is inside one (read, segment)
-        const int key = valid ? (r * 2 + seg) : -1;
-        const int key0 = __shfl(key, 0);
-        if (__all(key == key0)) {
-            int sum = sps;
-            for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
-            if ((tid & 63) == 0 && key0 >= 0) atomicAdd(&seglen[key0], (unsigned long long)sum);
-        } else if (valid) {
-            atomicAdd(&seglen[key], (unsigned long long)sps);
-        }
-    }
 }
 
 // ---- k_scan: sig_off = exclusive scan of per-read totals ------------------------------------
@@ -345,7 +259,7 @@ __device__ static inline void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// DW: 0 = dwell comes from memory (k_dwell ran) or is constant; 1 = drawn here, certified fp32 path with
+// DW: 0 = dwell comes from memory (an earlier pass drew it) or is constant; 1 = drawn here, certified fp32 path with
 // out-of-line FP64 fallback; 2 = drawn here in FP64 (src/gensig.c:254-257)
 // HIST: only the front half -- dwell draws, ranks, and the samples each k-mer stream is asked for, accumulated into the
 // workgroup's row (split chains, see above)

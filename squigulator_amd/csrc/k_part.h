@@ -8,8 +8,8 @@
 // rank >> 12, 64 of them for 9-mers), stably, and each bucket is walked against its own 4096-entry sub-row in LDS:
 //
 //   k_events<HIST, PART>  per link: dwell draws, ranks, events per (link, partition)                  -> pcnt
-//   k_part_offsets        per (worker chain, partition): pcnt -> first slot of every (link, partition) in part[]
-//   k_part_slices         the run of a (worker chain, partition) in part[] is cut into slices of equal length
+//   k_part_mid            per (worker chain, partition): pcnt -> first slot of every (link, partition) in part[]; the run of a (worker
+//                         chain, partition) in part[] is cut into slices of equal length (k_part_events.h; one partition: k_part_slices)
 //   k_events<PART>        per link: every event to its slot, {dwell, low 12 bits of the rank}; evrec = {slot, rank}
 //   k_part_hist           per slice: samples per stream over the slice                               -> phist
 //   k_part_scan           per (worker chain, rank): exclusive scan over the slices of the rank's partition on top of the
@@ -63,10 +63,6 @@ __device__ static inline void part_offsets_body(const int p, const int q, const 
         }
     }
     if (tid == 0) ptotal[(size_t)q * n_part + p] = total;
-}
-__global__ __launch_bounds__(1024) void k_part_offsets(const uint32_t* __restrict__ pcnt, uint32_t* __restrict__ poff, const int n_part, const int n_links,
-                                                       const int* __restrict__ wlink_off, uint32_t* __restrict__ ptotal) {
-    part_offsets_body(blockIdx.x, blockIdx.y, pcnt, poff, n_part, n_links, wlink_off, ptotal);
 }
 
 // The events of a (worker chain, partition) lie in part[] in the order the chain produces them; the hand-out walks them in that
@@ -139,7 +135,9 @@ __global__ __launch_bounds__(1024) void k_part_slices(uint32_t* pstart, const ui
     part_slice_bounds_wg(pstart, ptotal, n_pairs, slice_len, pfirst, slice_lo, slice_hi);
 }
 
-// one thread per slice (the host's bound)
+// one thread per slice (the host's bound).  No launch site since k_part_mid does this in its own launch; kept because without this
+// second caller of part_slice_bounds_one the compiler allocates the registers of k_part_slices and k_part_mid differently, and those
+// two are to stay as measured (profiles/variants_removed.md)
 __global__ __launch_bounds__(256) void k_part_slice_bounds(const uint32_t* __restrict__ pstart, const uint32_t* __restrict__ ptotal, const int n_pairs,
                                                            const uint32_t slice_len, const uint32_t* __restrict__ pfirst,
                                                            uint32_t* __restrict__ slice_lo, uint32_t* __restrict__ slice_hi) {
@@ -151,32 +149,7 @@ __global__ __launch_bounds__(256) void k_part_slice_bounds(const uint32_t* __res
 // grid: slices (the host's bound; the live ones are pfirst[n_pairs]), 256 threads.  phist[s][sub] <- samples the slice's events draw from the stream
 // (sums commute: a thread takes four consecutive records with one 16-B load -- 4-B loads stream at 4.0 TB/s on this machine, 16-B
 // loads at 6.3, tools/pmc_calib.hip -- 2048 events of the slice per step, the next step's loads in flight during this one's atomics)
-#ifndef PART_HIST_PAD
-#define PART_HIST_PAD 0          // A/B: words of LDS a workgroup reserves beyond its table (fewer workgroups per CU: whole rounds of slices)
-#endif
-#ifndef PART_HIST_V4
-#define PART_HIST_V4 1
-#endif
-#ifndef PART_NT
-#define PART_NT 0                // A/B (round 5): part[] read with non-temporal loads in k_part_hist / the hand-out (each record is read once per kernel)
-#endif
-typedef uint32_t part_u32x4 __attribute__((ext_vector_type(4)));
-__device__ static inline uint32_t part_ld(const uint32_t* p) {
-#if PART_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ static inline uint4 part_ld(const uint4* p) {
-#if PART_NT
-    const part_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const part_u32x4*>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
-}
-#define PART_LD(p_) part_ld(p_)
+__device__ static inline uint4 part_ld(const uint4* p) { return *p; }   // (a plain load; as a function: k_part_hist's code as measured)
 // Workgroups from `first_items` on (round 5) prepare the lean sample kernel's work items instead (items_body, k_samples.h: they need the
 // scan's offsets and the scatter pass' tile links, both complete before this launch, and nothing of this kernel): k_items as a launch of
 // its own was 15 us of work behind a launch gap.
@@ -184,24 +157,23 @@ __device__ static inline void items_body(const SigParams& P, const int block, co
 __global__ __launch_bounds__(256) void k_part_hist(const uint32_t* __restrict__ part, const uint32_t* __restrict__ slice_lo,
                                                    const uint32_t* __restrict__ slice_hi, const uint32_t* __restrict__ n_slices,
                                                    uint32_t* __restrict__ phist, const SigParams P, const int n_stiles, const unsigned first_items) {
-    __shared__ uint32_t row[PART_SUB + PART_HIST_PAD];
+    __shared__ uint32_t row[PART_SUB];
     const int tid = threadIdx.x;
     if (blockIdx.x >= first_items) { items_body(P, (int)(blockIdx.x - first_items), n_stiles); return; }
     if (blockIdx.x >= *n_slices) return;
     for (int i = tid; i < PART_SUB; i += 256) row[i] = 0u;
     __syncthreads();
     const uint32_t lo = slice_lo[blockIdx.x], hi = slice_hi[blockIdx.x];
-#if PART_HIST_V4
     // the slice from its first 16-B aligned record on in uint4s; the (up to three) records before that one by one
     const uint32_t lo4 = min((lo + 3u) & ~3u, hi);
     if (lo + (uint32_t)tid < lo4) { const uint32_t rec = part[lo + tid]; atomicAdd(&row[rec & (PART_SUB - 1)], rec >> 16); }
     const uint4* in = reinterpret_cast<const uint4*>(part + lo4) + tid;
     uint4 rec[2], nxt[2];
 #pragma unroll
-    for (int q = 0; q < 2; q++) rec[q] = PART_LD(in + 256 * q);              // (unconditional: PART_SLACK entries behind the last slice)
+    for (int q = 0; q < 2; q++) rec[q] = part_ld(in + 256 * q);              // (unconditional: PART_SLACK entries behind the last slice)
     for (uint32_t b = lo4; b < hi; b += 2048) {
 #pragma unroll
-        for (int q = 0; q < 2; q++) nxt[q] = PART_LD(in + 512 + 256 * q);
+        for (int q = 0; q < 2; q++) nxt[q] = part_ld(in + 512 + 256 * q);
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             const uint32_t w[4] = {rec[q].x, rec[q].y, rec[q].z, rec[q].w};
@@ -223,31 +195,6 @@ __global__ __launch_bounds__(256) void k_part_hist(const uint32_t* __restrict__ 
         for (int q = 0; q < 2; q++) rec[q] = nxt[q];
         in += 512;
     }
-#else
-    const uint32_t* in = part + lo + tid;
-    uint32_t rec[4], nxt[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) rec[q] = in[256 * q];                        // (unconditional: PART_SLACK entries behind the last slice)
-    for (uint32_t b = lo; b < hi; b += 1024) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) nxt[q] = in[1024 + 256 * q];             // the next step's records are in flight during this one's atomics
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const bool live = b + 256 * q + tid < hi;
-            const uint32_t sub = rec[q] & (PART_SUB - 1);
-            // a wavefront whose events all fall on one stream (poly-A tails ...): one add of the wavefront's sum instead of 64
-            // adds to one address
-            if (__builtin_amdgcn_ballot_w64(live && sub == (uint32_t)__builtin_amdgcn_readfirstlane((int)sub)) == ~0ull) {
-                int sum = (int)(rec[q] >> 16);
-                for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-                if ((tid & 63) == 0) atomicAdd(&row[sub], (uint32_t)sum);
-            } else if (live) atomicAdd(&row[sub], rec[q] >> 16);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) rec[q] = nxt[q];
-        in += 1024;
-    }
-#endif
     __syncthreads();
     uint32_t* dst = phist + (size_t)blockIdx.x * PART_SUB;
     for (int i = tid; i < PART_SUB; i += 256) dst[i] = row[i];
@@ -337,9 +284,6 @@ __global__ __launch_bounds__(256) void k_part_totals(const uint32_t* __restrict_
 #define PART_ATAGS 256
 #define PART_JT 256
 #define PART_STEP 1024
-#ifndef PART_ROW_CLAIMS
-#define PART_ROW_CLAIMS 1        // the first-try claims are written into the sub-row itself (no tag array: 18 instead of 26 KiB per wavefront)
-#endif
 #define PART_CLAIM 0x80000000u
 #define PART_CONTENDED 0xc0000000u
 #ifndef PART_ATOMIC_ROUNDS
@@ -355,9 +299,6 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
                                                   const uint32_t* __restrict__ n_slices,
                                                   const uint32_t* __restrict__ phist, const uint32_t* __restrict__ pw, const uint32_t dump) {
     __shared__ uint32_t row[PART_SUB];                            // stream states (< 2^31); during a phase also claims: PART_CLAIM | position
-#if !PART_ROW_CLAIMS
-    __shared__ uint16_t tg[PART_SUB];                             // position in the phase of the (last) event that took the tag; 0x100: contended
-#endif
     __shared__ uint32_t atg[PART_ATAGS];
     __shared__ uint32_t jt[PART_JT];                              // a^(2j)
     __shared__ uint32_t jt1[PART_JT];                             // a^(2*256*j): with jt, any jump below 65536 samples without leaving LDS
@@ -399,7 +340,6 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
                 mul[q] = jt[d & (PART_JT - 1)];
                 if (BIGD && d >= PART_JT) mul[q] = lcg_jump2(pw, d);
             }
-#if PART_ROW_CLAIMS
             // the claims live in the sub-row itself (a state never has bit 31): every event reads its stream's state, THEN writes
             // its claim over it; whoever still finds its own claim after the others marked theirs "contended" is alone
 #pragma unroll
@@ -420,27 +360,6 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
                     pend[q] = false;
                 }
             }
-#else
-#pragma unroll
-            for (int q = 0; q < 4; q++) if (pend[q]) __hip_atomic_store(&tg[sub[q]], pri[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            uint16_t t[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) t[q] = __hip_atomic_load(&tg[sub[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#pragma unroll
-            for (int q = 0; q < 4; q++) if (pend[q] && t[q] != pri[q]) __hip_atomic_store(&tg[sub[q]], (uint16_t)0x100, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                t[q] = __hip_atomic_load(&tg[sub[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                st[q] = __hip_atomic_load(&row[sub[q]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if (pend[q] && t[q] == pri[q]) {                   // alone on the stream in this phase
-                    __hip_atomic_store(&row[sub[q]], lcg_mul(st[q], mul[q]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                    pend[q] = false;
-                }
-            }
-#endif
             int round = 0;
             for (;;) {                                               // contended streams, in order
                 const int n_pend = __builtin_popcountll(__builtin_amdgcn_ballot_w64(pend[0])) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(pend[1])) +
@@ -460,9 +379,7 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         if (pend[q] && ta[q] == (uint32_t)pri[q]) {
-#if PART_ROW_CLAIMS
                             if (s0[q] & PART_CLAIM) s0[q] = st[q];  // the stream's first event of the phase: the row still holds a claim, the state is the one read before
-#endif
                             __hip_atomic_store(&row[sub[q]], lcg_mul(s0[q], mul[q]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                             __hip_atomic_store(&atg[sub[q] & (PART_ATAGS - 1)], 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                             st[q] = s0[q];
@@ -481,13 +398,11 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
                 const uint32_t sub_sel = ql == 0 ? sub[0] : ql == 1 ? sub[1] : ql == 2 ? sub[2] : sub[3];
                 const uint32_t sstar = (uint32_t)__shfl((int)sub_sel, ll);
                 uint32_t sv = __hip_atomic_load(&row[sstar], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#if PART_ROW_CLAIMS
                 {   // (the row may still hold a claim: the state is then the one the stream's events read before claiming)
                     const uint32_t st_sel = ql == 0 ? st[0] : ql == 1 ? st[1] : ql == 2 ? st[2] : st[3];
                     const uint32_t s_lead = (uint32_t)__shfl((int)st_sel, ll);
                     if (sv & PART_CLAIM) sv = s_lead;
                 }
-#endif
                 uint32_t run = 0;                                    // samples of the stream's earlier events of the phase
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -525,9 +440,6 @@ __global__ __launch_bounds__(64) void k_part_hand(const uint32_t* __restrict__ p
 // atomics cost the LDS: one address, one lane after the other.
 // a^(2n) comes from three 256-entry tables in LDS (n < 2^24: a stream's samples in one slice; else the global tables).
 #define PART_LT 256
-#ifndef HAND_ABL
-#define HAND_ABL 0
-#endif
 #ifndef HAND_STEP
 #define HAND_STEP 1024          // events per step of k_part_hand_ord (A/B: 2048 -- twice the loads in flight; a slice is a multiple of PART_STEP)
 #endif
@@ -564,14 +476,14 @@ __device__ static __forceinline__ void hand_slice(HandLds& H, const uint32_t* __
     uint32_t* out_p = state_out + lo + lane;
     uint32_t cur[NR], nxt[NR];
 #pragma unroll
-    for (int r = 0; r < NR; r++) cur[r] = PART_LD(in + 64 * r);     // (unconditional: PART_SLACK entries behind the last slice)
+    for (int r = 0; r < NR; r++) cur[r] = in[64 * r];               // (unconditional: PART_SLACK entries behind the last slice)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // one step: event 64 r + lane is the lane's r-th -- instruction order, then lane order
     auto step = [&](auto full_tag, auto check_tag, const uint32_t left) {
         constexpr bool FULL = decltype(full_tag)::value, CHECK = decltype(check_tag)::value;
 #pragma unroll
-        for (int r = 0; r < NR; r++) nxt[r] = PART_LD(in + HAND_STEP + 64 * r);
+        for (int r = 0; r < NR; r++) nxt[r] = in[HAND_STEP + 64 * r];
         uint32_t n[NR], out[NR];
         if (CHECK && fault) {                                       // (test hook) rows 0 and 1 in the wrong order
             const uint32_t t = cur[0]; cur[0] = cur[1]; cur[1] = t;
@@ -579,12 +491,8 @@ __device__ static __forceinline__ void hand_slice(HandLds& H, const uint32_t* __
 #pragma unroll
         for (int r = 0; r < NR; r++) {
             n[r] = 0;
-#if HAND_ABL == 1      /* timing-only ablation: no atomics */
-            n[r] = cur[r] & 7u;
-#else
             if (FULL || (uint32_t)(64 * r + lane) < left) n[r] = __hip_atomic_fetch_add(&cnt[cur[r] & (PART_SUB - 1)], cur[r] >> 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             asm volatile("" ::: "memory");                          // (the compiler keeps the atomics in this order)
-#endif
         }
         if (CHECK && fault) {
             const uint32_t t = cur[0]; cur[0] = cur[1]; cur[1] = t;
@@ -635,16 +543,8 @@ __device__ static __forceinline__ void hand_slice(HandLds& H, const uint32_t* __
                 }
             }
         }
-#if HAND_ABL == 2      /* timing-only ablation: no stores */
-        if (out[0] == 0x12345u) out_p[0] = out[1] ^ out[NR - 1];
-#elif defined(SQG_ABL_HANDOVER)   /* timing-only ablation (round 5, results wrong): 16 B per slot -- the state with the stream's pore-table row -- as the
-                                     hand-over of round 4's review would write them (the row itself is NOT looked up: what is priced is the traffic) */
-#pragma unroll
-        for (int r = 0; r < NR; r++) if (FULL || (uint32_t)(64 * r + lane) < left) reinterpret_cast<uint4*>(state_out)[(size_t)(out_p - state_out) + 64 * r] = make_uint4(out[r], cur[r], n[r], out[r] ^ cur[r]);
-#else
 #pragma unroll
         for (int r = 0; r < NR; r++) if (FULL || (uint32_t)(64 * r + lane) < left) out_p[64 * r] = out[r];
-#endif
 #pragma unroll
         for (int r = 0; r < NR; r++) cur[r] = nxt[r];
         in += HAND_STEP; out_p += HAND_STEP;

@@ -33,12 +33,6 @@
 #define PEV_COUNT_OCC 1                  // first pass: wavefronts per SIMD the register allocation aims at
 #endif
 #define PEV_WAVES_SCATTER 2              // ... second pass (10 KiB of LDS per link)
-#ifndef PEV_PACK_SUMS
-#define PEV_PACK_SUMS 1                  // two tile sums per DPP scan (A/B)
-#endif
-#ifndef PEV_SCATTER_FASTRANK
-#define PEV_SCATTER_FASTRANK 0          // A/B: the scatter pass with the per-segment test of the rank look-up as well
-#endif
 #define PEV_HALO 24                      // bases behind the segment's own: 2 (k - 1) <= 16 (the k-mers of the RNA stall start k - 1 bases further on)
 #define PEV_WORDS ((PEV_SEG + PEV_HALO) / 16 + 2)
 
@@ -211,7 +205,7 @@ __device__ static __forceinline__ void pev_link(const SigParams& P, const PevTab
             // (wave-uniform) does the read's second part -- the RNA stall behind the adaptor -- start inside this segment?  Else event j's
             // k-mer starts at base j of the segment: word and shift depend on (q, lane) alone and cost the segment nothing (with the
             // test per event: 9 of the pass's 60 VALU instructions per event)
-            const bool straddle = (SCATTER && !PEV_SCATTER_FASTRANK) || (rd.ne1 > 0 && s0 < rd.ne0 && s0 + PEV_SEG > rd.ne0);   // (the scatter pass is not short of VALU cycles, and the second copy of the loop costs it 15 registers)
+            const bool straddle = SCATTER || (rd.ne1 > 0 && s0 < rd.ne0 && s0 + PEV_SEG > rd.ne0);   // (the scatter pass is not short of VALU cycles, and the second copy of the loop costs it 15 registers)
             if (!straddle) {
 #pragma unroll
                 for (int q = 0; q < PEV_EPL; q++) {
@@ -267,7 +261,7 @@ __device__ static __forceinline__ void pev_link(const SigParams& P, const PevTab
                 // (the samples of each of the segment's eight tiles: a sum over the wavefront -- two tiles per DPP scan, 16 bits each,
                 // while 64 dwells fit 16 bits: 7 of the pass's 69 instructions per event)
                 uint32_t tsum[PEV_EPL];
-                if (PEV_PACK_SUMS && P.dwell_pack) {
+                if (P.dwell_pack) {
                     static_assert(PEV_EPL == 8, "four packed sums");
                     int two[4];
 #pragma unroll
@@ -398,9 +392,6 @@ __global__ __launch_bounds__(64 * (MODE == PEV_SCATTER ? PEV_WAVES_SCATTER : PEV
 #ifndef PHC_COUNT_WAVES
 #define PHC_COUNT_WAVES 3
 #endif
-#ifndef PHC_PRIO
-#define PHC_PRIO 0                       // A/B: the hand-out wavefront at a raised issue priority (s_setprio)
-#endif
 template <int DW, int MODE>
 __global__ __launch_bounds__(64 * (1 + PHC_COUNT_WAVES), 4) void k_part_hand_count(
         const uint32_t* __restrict__ part, uint32_t* __restrict__ state_out, const uint32_t* __restrict__ slice_lo, const uint32_t* __restrict__ slice_hi,
@@ -431,9 +422,6 @@ __global__ __launch_bounds__(64 * (1 + PHC_COUNT_WAVES), 4) void k_part_hand_cou
     // atomics on one cache line took longer than the work they handed out (the fused launch 705 us against 296 + 285 for the two
     // kernels one after the other)
     if (wid == hw) {
-#if PHC_PRIO
-        __builtin_amdgcn_s_setprio(PHC_PRIO);
-#endif
         const uint32_t ns = *n_slices;
         for (uint32_t sl = blockIdx.x; sl < ns; sl += gridDim.x)
             hand_slice(H, part, state_out, slice_lo[sl], slice_hi[sl], phist + (size_t)sl * PART_SUB, pw, err, fault, lane);
@@ -464,7 +452,7 @@ __device__ static inline void part_tile_bases_body(const SigParams& P, const int
 __global__ __launch_bounds__(64) void k_part_tile_bases(const SigParams P) { part_tile_bases_body(P, blockIdx.x, threadIdx.x); }
 
 // What lies between the two event passes in ONE launch (each of the four kernels it replaces is a few microseconds of work behind
-// a launch: 25 us of a 1000-read batch's 360): workgroups [0, n_off) do k_part_offsets' (partition, worker chain) pairs, the
+// a launch: 25 us of a 1000-read batch's 360): workgroups [0, n_off) do the offsets of the (partition, worker chain) pairs (part_offsets_body), the
 // ones behind them k_part_tile_bases' pieces (a wavefront each); the offsets workgroup that finishes LAST -- a counter, agent-scope
 // release / acquire: the others' totals are then visible to it -- goes on to k_part_slices and the slices' bounds.
 __global__ __launch_bounds__(1024) void k_part_mid(const SigParams P, const uint32_t* __restrict__ pcnt, uint32_t* __restrict__ poff, const int n_part, const int n_links,

@@ -2,9 +2,8 @@
 // k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h and k_blow5.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
-//   k_dwell       per-event dwell draw from the worker's time stream   (src/gensig.c:254-257)
 //   k_scan        read lengths -> output offsets
-//   k_events      per worker chain: ranks, in-order hand-out of the k-mer streams
+//   k_events      per worker chain: dwell draws (src/gensig.c:254-257), ranks, in-order hand-out of the k-mer streams
 //   k_part_*      k > 6, few workers: the stream hand-out over events bucketed by the top bits of the rank (k_part.h)
 //   k_samples     per 64-event tile: the samples                       (src/gensig.c:226-356)
 //   k_fixup       FP64 recomputation of the samples the certified fp32 path could not decide

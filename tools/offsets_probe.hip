@@ -1,4 +1,4 @@
-// k_part_offsets alone on synthetic counts: where do its 30 us go?   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I squigulator_amd/csrc tools/offsets_probe.hip -o /tmp/op
+// the offsets pass of k_part_mid (part_offsets_body) alone on synthetic counts: where do its 30 us go?   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I squigulator_amd/csrc tools/offsets_probe.hip -o /tmp/op
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
@@ -7,6 +7,11 @@
 #include "k_common.h"
 #include "k_events.h"
 #include "k_part.h"
+#include "k_samples.h"
+__global__ __launch_bounds__(1024) void k_part_offsets(const uint32_t* __restrict__ pcnt, uint32_t* __restrict__ poff, const int n_part, const int n_links,
+                                                       const int* __restrict__ wlink_off, uint32_t* __restrict__ ptotal) {
+    part_offsets_body(blockIdx.x, blockIdx.y, pcnt, poff, n_part, n_links, wlink_off, ptotal);
+}
 __global__ __launch_bounds__(1024) void empty1024(uint32_t* p) { if (p == nullptr) *p = 0; }
 __global__ __launch_bounds__(1024) void touch(const uint32_t* __restrict__ pcnt, uint32_t* __restrict__ out, int n_links) {
     const uint32_t* row = pcnt + (size_t)blockIdx.x * n_links;
