@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h and include/sqg_chunks.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -90,7 +90,27 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
-             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS")
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC")
+
+# include/sqg_chunks.h: bound by load_library only when the library has them (the CPU backend does not)
+EXPORTS_CHUNKS = ("sqg_chunk_plan", "sqg_batch_chunks")
+CHUNK_F16, CHUNK_F32 = 0, 1
+CHUNK_MEDMAD, CHUNK_PA = 0, 1
+
+
+class CChunkCfg(C.Structure):
+    _fields_ = [("chunk_len", C.c_int32), ("stride", C.c_int32), ("max_label", C.c_int32), ("dtype", C.c_uint32), ("norm", C.c_uint32)]
+
+
+class CChunkOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("signal", "labels", "label_len", "chunk_read", "chunk_start", "med2", "mad4")]
+
+
+class Chunks:
+    """What Batch.chunks() returns: torch tensors on the context's device (include/sqg_chunks.h says what they hold)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
 
 _libs = {}                  # absolute path -> loaded library
 LOADED_PATH = None          # the library the last load_library() call opened (bench.py prints it with its hash)
@@ -203,6 +223,11 @@ def load_library(path: str | None = None):
     L.sqg_set_stage_threads.argtypes = [vp, C.c_int]
     L.sqg_build_info.restype = C.c_char_p
     L.sqg_build_info.argtypes = []
+    if all(hasattr(L, n) for n in EXPORTS_CHUNKS):
+        L.sqg_chunk_plan.restype = C.c_int
+        L.sqg_chunk_plan.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(i64), C.POINTER(i64)]
+        L.sqg_batch_chunks.restype = C.c_int
+        L.sqg_batch_chunks.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
     _libs[path] = L
     return L
 
@@ -406,6 +431,67 @@ class Batch:
         data = C.string_at(recs, nb.value) if nb.value else b""
         return data, np.array([ro[i] for i in range(len(read_ids) + 1)], np.int64)
 
+    def signal_tensor(self):
+        """zero-copy torch.int16 view of the batch's samples on the device (sqg_result_t.d_signal); valid as long as the batch's device
+        results are (include/sqg.h: until two more batches have been run); the view keeps the batch alive"""
+        import torch
+        if self.res is None:
+            self.wait()
+        dev = torch.device("cuda", self.gen.device)
+        if self.n_samples == 0:
+            return torch.empty(0, dtype=torch.int16, device=dev)
+        if not self.res.d_signal:
+            raise SqgError(-4, "signal_tensor", "the batch's device results have been handed to a later batch")
+
+        class _View:                                       # (the owner torch keeps: the batch stays alive with the tensor)
+            def __init__(self, batch, ptr, n):
+                self.batch = batch
+                self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i2", "data": (ptr, False), "version": 2}
+        return torch.as_tensor(_View(self, int(self.res.d_signal), int(self.n_samples)), device=dev)
+
+    def _chunk_cfg(self, chunk_len, stride, max_label, dtype, norm):
+        if not hasattr(self.gen.L, "sqg_batch_chunks"):
+            raise SqgError(-1, "chunks", "this backend has no sqg_batch_chunks (include/sqg_chunks.h)")
+        dt = {"f16": CHUNK_F16, "f32": CHUNK_F32}.get(dtype, dtype)
+        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
+        if not isinstance(dt, int) or not isinstance(nm, int):
+            raise SqgError(-1, "chunks", f"unknown dtype / norm {dtype!r} / {norm!r}")
+        return CChunkCfg(int(chunk_len), int(chunk_len if stride is None else stride), int(max_label), dt & 0xffffffff, nm & 0xffffffff)
+
+    def chunk_plan(self, chunk_len: int, stride: int | None = None):
+        """(chunk_off [n_reads+1], n_chunks): the first chunk of every read, from the batch's sig_off (sqg_chunk_plan; host only)"""
+        cfg = self._chunk_cfg(chunk_len, stride, 0, CHUNK_F16, CHUNK_MEDMAD)
+        off = np.zeros(self.n_reads + 1, np.int64)
+        nc = C.c_int64()
+        self.gen._chk(self.gen.L.sqg_chunk_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nc)),
+                      "sqg_chunk_plan")
+        return off, int(nc.value)
+
+    def chunks(self, chunk_len: int, stride: int | None = None, max_label: int = 0, dtype="f16", norm="medmad",
+               signal: bool = True, labels: bool = True) -> Chunks:
+        """Fixed-length, per-read normalised windows of the batch's signal and their base labels, made on the device
+        (sqg_batch_chunks): torch tensors signal [n_chunks, L] (float16 / float32), labels [n_chunks, W] (uint8, 0 = padding),
+        label_len, chunk_read, chunk_start [n_chunks], med2, mad4 [n_reads].  signal=False / labels=False leave those passes out
+        (the tensors are then None)."""
+        import torch
+        cfg = self._chunk_cfg(chunk_len, stride, max_label, dtype, norm)
+        off, nc = self.chunk_plan(chunk_len, cfg.stride)
+        dev = torch.device("cuda", self.gen.device)
+        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev) if nc == 0 else torch.empty(shape, dtype=dt, device=dev)   # noqa: E731
+        ch = Chunks(n_chunks=nc, chunk_off=off,
+                    signal=new((nc, cfg.chunk_len), torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16) if signal else None,
+                    labels=new((nc, cfg.max_label), torch.uint8) if labels else None,
+                    label_len=new((nc,), torch.int32) if labels else None,
+                    chunk_read=new((nc,), torch.int32), chunk_start=new((nc,), torch.int64),
+                    med2=torch.zeros(self.n_reads, dtype=torch.int32, device=dev), mad4=torch.zeros(self.n_reads, dtype=torch.int32, device=dev))
+        if nc == 0:
+            return ch
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None          # noqa: E731
+        out = CChunkOut(ptr(ch.signal), ptr(ch.labels), ptr(ch.label_len), ptr(ch.chunk_read), ptr(ch.chunk_start), ptr(ch.med2), ptr(ch.mad4))
+        torch.cuda.synchronize(dev)                         # (the allocator's pending work on these blocks, if any, before another stream writes them)
+        self.gen._chk(self.gen.L.sqg_batch_chunks(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_chunks")
+        return ch
+
     def free(self):
         if self.handle:
             self.gen.L.sqg_batch_free(self.gen.ctx, self.handle)
@@ -443,6 +529,7 @@ class SignalGenerator:
             raise SqgError(rc, "sqg_create", self.L.sqg_strerror(rc).decode())
         self.ctx = h
         self.num_workers, self.kmer_size, self.flags, self.profile = num_workers, kmer_size, flags, profile
+        self.device = device
 
     def _chk(self, rc, where):
         if rc != 0:

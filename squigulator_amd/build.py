@@ -29,9 +29,10 @@ import hashlib
 
 
 def headers() -> list:
-    """every header the one translation unit includes: include/sqg.h and all of csrc/*.h (globbed: a new header is a dependency
+    """every header the one translation unit includes: include/sqg.h, include/sqg_chunks.h and all of csrc/*.h (globbed: a new header is a dependency
     the moment it exists)"""
-    return [os.path.join(os.path.dirname(HERE), "include", "sqg.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    return [os.path.join(inc, "sqg.h"), os.path.join(inc, "sqg_chunks.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
 
 
 def source_hash() -> str:

@@ -1,0 +1,126 @@
+// h_chunks.h -- sqg_chunk_plan, sqg_batch_chunks: labelled, normalised chunks of a batch's signal, left on the device
+// Host side of include/sqg_chunks.h; included by sqg_hip.hip (one translation unit with the kernels), in the order listed there.
+#pragma once
+
+static int chunk_check(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, const char* who) {
+    if (!c) return SQG_EINVAL;
+    auto bad = [&](const char* what) { c->err = std::string(who) + ": " + what; return SQG_EINVAL; };
+    if (!b || !cfg) return bad("batch and cfg must not be NULL");
+    if (c->cfg.flags & SQG_PREFIX) return bad("chunks: not with SQG_PREFIX");
+    if (cfg->chunk_len < 64 || cfg->chunk_len > (1 << 20) || (cfg->chunk_len & 7)) return bad("chunk_len must be a multiple of 8 in 64 .. 1<<20");
+    if (cfg->stride < 1) return bad("stride must be >= 1");
+    if (cfg->max_label < 0 || cfg->max_label > 65535) return bad("max_label must be in 0 .. 65535");
+    if (cfg->dtype != SQG_CHUNK_F16 && cfg->dtype != SQG_CHUNK_F32) return bad("unknown dtype");
+    if (cfg->norm != SQG_CHUNK_MEDMAD && cfg->norm != SQG_CHUNK_PA) return bad("unknown norm");
+    if (!b->ran) { c->err = std::string(who) + ": the batch has not been run"; return SQG_ESEQUENCE; }
+    return SQG_OK;
+}
+
+// chunk_off [n+1] from the batch's sig_off (the batch has been waited for); a read shorter than a k-mer has no chunks
+static void chunk_plan(const sqg_batch* b, const sqg_chunk_cfg_t* cfg, long long* off) {
+    const long long L = cfg->chunk_len, S = cfg->stride;
+    off[0] = 0;
+    for (int i = 0; i < b->n; i++) {
+        const long long n = b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i];
+        const bool none = n < L || ((size_t)i < b->short_read.size() && b->short_read[(size_t)i]);
+        off[i + 1] = off[i] + (none ? 0 : (n - L) / S + 1);
+    }
+}
+
+extern "C" int sqg_chunk_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_t* cfg, int64_t* chunk_off, int64_t* n_chunks) {
+    int rc = chunk_check(c, b, cfg, "sqg_chunk_plan");
+    if (rc) return rc;
+    if (!n_chunks) { c->err = "sqg_chunk_plan: n_chunks must not be NULL"; return SQG_EINVAL; }
+    if ((rc = sqg_batch_wait(c, b, nullptr))) return rc;
+    std::vector<long long>& off = c->h_chunk_off;
+    off.resize((size_t)b->n + 1);
+    chunk_plan(b, cfg, off.data());
+    if (chunk_off) for (int i = 0; i <= b->n; i++) chunk_off[i] = (int64_t)off[(size_t)i];
+    *n_chunks = (int64_t)off[(size_t)b->n];
+    return SQG_OK;
+}
+
+extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_t* cfg, const sqg_chunk_out_t* out) {
+    int rc = chunk_check(c, b, cfg, "sqg_batch_chunks");
+    if (rc) return rc;
+    if (!out) { c->err = "sqg_batch_chunks: out must not be NULL"; return SQG_EINVAL; }
+    if (out->signal && ((uintptr_t)out->signal & 15)) { c->err = "sqg_batch_chunks: signal must be 16-byte aligned"; return SQG_EINVAL; }
+    const bool need_dwell = c->use_dwell_stream && (out->labels || out->label_len);
+    if (b->run_idx + 2 < c->runs || !slot_is_mine(c, b) || (need_dwell && !cset_is_mine(c, b))) {
+        c->err = "sqg_batch_chunks: the batch's device results have been handed to a later batch";
+        return SQG_ESEQUENCE;
+    }
+    if ((rc = sqg_batch_wait(c, b, nullptr))) return rc;                 // waits for the batch's own kernels; fills sig_off
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int n = b->n;
+    if (n == 0) return SQG_OK;
+    sqg_ctx::Slot& Z = c->slot[b->slot];
+    std::vector<long long>& off = c->h_chunk_off;
+    off.resize((size_t)n + 1);
+    chunk_plan(b, cfg, off.data());
+    const long long n_chunks = off[(size_t)n];
+
+    ChunkParams P{};
+    P.sig = Z.d_sig; P.sig_off = Z.d_sigoff; P.n_reads = n; P.n_chunks = n_chunks;
+    P.L = cfg->chunk_len; P.S = cfg->stride; P.W = cfg->max_label;
+    P.hist_max = CHUNK_HIST; P.one_wg_max = 1LL << 22;
+    // development build: 1 sends every read through the wide path (global histograms), 2 through the long one (several workgroups per read)
+    const int force = dev_env_int(SQG_DEV_ENV("SQG_TEST_CHUNK_GENERIC"), 0);
+    if (force == 1) P.hist_max = 0;
+    if (force == 2) P.one_wg_max = 0;
+    P.med2 = out->med2; P.mad4 = out->mad4;
+    P.chunk_read_out = out->chunk_read; P.chunk_start_out = (long long*)out->chunk_start;
+    P.range = c->cfg.profile.range; P.dig = c->cfg.profile.digitisation;
+
+    if ((rc = ensure(c, (void**)&c->d_chunk_off, &c->chunk_off_cap, (size_t)n + 1, sizeof(long long)))) return rc;
+    if ((rc = ensure(c, (void**)&c->d_chunk_const, &c->chunk_const_cap, (size_t)n, sizeof(float2)))) return rc;
+    if ((rc = ensure(c, (void**)&c->d_chunk_wide, &c->chunk_wide_cap, (size_t)n + 1, sizeof(unsigned int)))) return rc;
+    if ((rc = ensure(c, (void**)&c->d_chunk_ghist, &c->chunk_ghist_cap, (size_t)CHUNK_WIDE_SLOTS * 2 * CHUNK_GBINS, sizeof(unsigned int)))) return rc;
+    if ((rc = ensure(c, (void**)&c->d_chunk_read, &c->chunk_read_cap, (size_t)n_chunks + 1, sizeof(int)))) return rc;
+    const bool want_labels = n_chunks > 0 && ((out->labels && cfg->max_label > 0) || out->label_len);
+    if (want_labels && (rc = ensure(c, (void**)&c->d_chunk_ev, &c->chunk_ev_cap, (size_t)n_chunks, sizeof(int2)))) return rc;
+    P.chunk_off = c->d_chunk_off; P.consts = c->d_chunk_const; P.wide_list = c->d_chunk_wide; P.ghist = c->d_chunk_ghist;
+    P.chunk_read = c->d_chunk_read;
+
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->d_chunk_off, off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    // pass 1, statistics: the read's constants for the emit kernel, med2 / mad4 for the caller
+    const bool want_stats = out->med2 || out->mad4 || (out->signal && n_chunks > 0 && cfg->norm == SQG_CHUNK_MEDMAD);
+    if (want_stats) {
+        HIPCHK(c, hipMemsetAsync(c->d_chunk_wide, 0, sizeof(unsigned int), st));
+        hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
+        hipLaunchKernelGGL(k_chunk_stats_wide, dim3(CHUNK_WIDE_SLOTS), dim3(CHUNK_WG), 0, st, P);
+        for (int i = 0; i < n; i++) {
+            const long long ns = b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i];
+            if (ns <= 0 || ns <= P.one_wg_max) continue;
+            HIPCHK(c, hipMemsetAsync(c->d_chunk_ghist, 0, (size_t)2 * CHUNK_GBINS * sizeof(unsigned int), st));
+            const unsigned wgs = (unsigned)std::min<long long>((ns + 16 * CHUNK_WG - 1) / (16 * CHUNK_WG), 4LL * c->num_cu);
+            hipLaunchKernelGGL(k_chunk_hist_long, dim3(wgs), dim3(CHUNK_WG), 0, st, P, i);
+            hipLaunchKernelGGL(k_chunk_select_long, dim3(1), dim3(CHUNK_WG), 0, st, P, i);
+        }
+        HIPCHK(c, hipGetLastError());
+        if ((rc = dbg_sync(c, "k_chunk_stats"))) return rc;
+    }
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(k_chunk_index, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
+        // pass 2, emit
+        if (out->signal) {
+            const int g8 = P.L >> 3, cpb = g8 >= CHUNK_WG ? 1 : CHUNK_WG / g8;
+            const unsigned wgs = (unsigned)std::min<long long>((n_chunks + cpb - 1) / cpb, 1LL << 20);
+            const bool f32 = cfg->dtype == SQG_CHUNK_F32, pa = cfg->norm == SQG_CHUNK_PA;
+#define CHUNK_EMIT(F, A) hipLaunchKernelGGL((k_chunk_emit<F, A>), dim3(wgs), dim3(CHUNK_WG), 0, st, P, (const ReadDesc*)b->d_reads, out->signal)
+            if (f32) { if (pa) CHUNK_EMIT(true, true); else CHUNK_EMIT(true, false); }
+            else { if (pa) CHUNK_EMIT(false, true); else CHUNK_EMIT(false, false); }
+#undef CHUNK_EMIT
+        }
+        // pass 3, labels
+        if (want_labels)
+            hipLaunchKernelGGL(k_chunk_labels, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P, (const ReadDesc*)b->d_reads, (const uint8_t*)b->d_bases,
+                               c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr, (int)c->cfg.profile.dwell_mean,
+                               (c->cfg.flags & SQG_RNA) ? 1 : 0, (c->cfg.flags & SQG_METH) ? 1 : 0, c->d_chunk_ev,
+                               cfg->max_label > 0 ? out->labels : (uint8_t*)nullptr, out->label_len);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SQG_OK;
+}

@@ -210,6 +210,15 @@ struct sqg_ctx {
     // (profiles/r05_summary.md); the first large batches of a context time the pass itself on three more allocations per slot and keep the best
     int cal_runs_left = 12;
     void* b5_reader = nullptr; int b5_reader_buf = -1; void (*b5_reader_drain)(void* writer, bool unbind) = nullptr;
+    // sqg_batch_chunks (h_chunks.h): first chunk of every read, the reads' {median, 1 / (1.4826 MAD)}, chunk -> read, every chunk's event range,
+    // the list of reads whose codes span more than the LDS histogram, the global histograms of the generic statistics paths
+    long long* d_chunk_off = nullptr; size_t chunk_off_cap = 0;
+    float2* d_chunk_const = nullptr; size_t chunk_const_cap = 0;
+    int* d_chunk_read = nullptr; size_t chunk_read_cap = 0;
+    int2* d_chunk_ev = nullptr; size_t chunk_ev_cap = 0;
+    unsigned int* d_chunk_wide = nullptr; size_t chunk_wide_cap = 0;
+    unsigned int* d_chunk_ghist = nullptr; size_t chunk_ghist_cap = 0;
+    std::vector<long long> h_chunk_off;
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };
@@ -255,6 +264,7 @@ struct sqg_batch {
     // (the same allocation ends with SQG_HRES_LL words for k_fixup's report: error word, fix-up counts -- SigParams.host_res)
     long long n_bases_total = 0;         // bytes in d_bases
     std::vector<long long> h_base_off;   // per read: its segment 0 in d_bases
+    std::vector<uint8_t> short_read;     // per read: shorter than a k-mer, the stand-in sequence of src/gensig.c:242-245 was generated (no chunks: h_chunks.h)
     std::vector<int32_t> s_ref_idx, s_ref_len, s_ref_pos, s_rlen;   // sqg_batch_sample: what gen_read returned
     std::vector<char> s_strand;
     std::vector<long long> s_src;                                   // where each sampled read starts in the resident genome

@@ -140,7 +140,7 @@ struct Staging {
             long long len0 = len;
             if (prefix) len0 += rna ? (kPolyA + (long long)strlen(kAdaptorRna)) : ((long long)strlen(kStallDna) + (long long)strlen(kAdaptorDna));
             int ne0, l0;
-            if (len0 < k) { ne0 = 5; l0 = 5 + k - 1; }                  // src/gensig.c:242-245
+            if (len0 < k) { ne0 = 5; l0 = 5 + k - 1; b->short_read.resize((size_t)n, 0); b->short_read[(size_t)i] = 1; }   // src/gensig.c:242-245
             else { ne0 = (int)(len0 - k + 1); l0 = (int)len0; }
             int ne1 = 0, l1 = 0;
             if (prefix && rna) { l1 = (int)strlen(kStallRna); ne1 = l1 - k + 1; }   // src/genread.c:87-88

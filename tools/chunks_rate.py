@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""Rate of sqg_batch_chunks (include/sqg_chunks.h) on the headline workload's shape: K sampled 10-kb reads, -x dna-r10-prom, -t 1.
+Per setting: the blocking call's wall-clock milliseconds (median of the timed calls, after a warm-up call), next to the same batch's
+generation time (sqg_timing_t.total_ms), and the bytes the call must move (2 N + dtype_bytes L n_chunks + W n_chunks) over that time,
+next to the streaming-store rate sqg_probe_store_bandwidth reports in the same run.  Prints a markdown table (profiles/chunks.md).
+usage: python tools/chunks_rate.py [reads_per_batch=32768] [timed_calls=5] [genome_mb]"""
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402  (first: the HIP runtime torch brings is the one the library then uses)
+
+torch.zeros(1, device="cuda")
+import bench  # noqa: E402
+from squigulator_amd import api, model, profiles  # noqa: E402
+
+K = int(sys.argv[1]) if len(sys.argv) > 1 else 32768
+REP = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+MB = float(sys.argv[3]) if len(sys.argv) > 3 else None
+prof, fl = profiles.get_profile("dna-r10-prom")
+mean, stdv = model.synthetic_model(9)
+dev = torch.device("cuda", 0)
+seq, lens = bench.synthetic_genome_device(MB, dev)
+gen = api.SignalGenerator(prof, fl, 9, mean, stdv, 42, num_workers=1, mode=api.MODE_CERTIFIED)
+gen.load_genome_device(seq.data_ptr(), lens, 10000, api.SAMPLE_DNA)
+workers = np.zeros(K, np.int32)
+for _ in range(2):                                          # warm-up batches (allocation, placement calibration starts)
+    gen.sample(K, workers).run().wait().free()
+b = gen.sample(K, workers).run().wait()
+gen_ms = gen.timing()["total_ms"]
+N = int(b.n_samples)
+store = gen.probe_store_bandwidth(1 << 30, 10)
+L, W = 4096, 512
+print(f"# sqg_batch_chunks on one MI355X: {K} sampled 10-kb reads (dna-r10-prom, -t 1, certified), N = {N:.4g} samples\n")
+print(f"generation of this batch (sqg_timing_t.total_ms): {gen_ms:.2f} ms; streaming-store probe: {store / 1e12:.2f} TB/s; "
+      f"median of {REP} timed calls after one warm-up call, wall clock around the blocking call\n")
+print("| setting | chunks | call ms | generation ms | bytes moved | GB/s | of the store probe |")
+print("|---|---|---|---|---|---|---|")
+for name, S, kw in (("L 4096, S = L, f16 medmad, W 512", L, {}), ("L 4096, S = L/2, f16 medmad, W 512", L // 2, {}),
+                    ("statistics pass alone (signal = labels = NULL)", L, dict(signal=False, labels=False)),
+                    ("statistics + emit, S = L (labels = NULL)", L, dict(labels=False)),
+                    ("statistics + labels, S = L (signal = NULL)", L, dict(signal=False))):
+    ts = []
+    for it in range(REP + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ch = b.chunks(L, S, W, **kw)
+        ts.append((time.perf_counter() - t0) * 1e3)
+        nc = ch.n_chunks
+        del ch
+    ms = float(np.median(ts[1:]))
+    moved = 2 * N + (2 * L * nc if kw.get("signal", True) else 0) + (W * nc if kw.get("labels", True) else 0)
+    print(f"| {name} | {nc} | {ms:.2f} (min {min(ts[1:]):.2f}, max {max(ts[1:]):.2f}) | {gen_ms:.2f} | {moved / 1e9:.2f} GB | {moved / ms / 1e6:.0f} | {moved / (ms * 1e-3) / store:.2f} |")
+b.free()
+gen.close()
