@@ -2,7 +2,8 @@
 
 CPU: the oracle restatement against bytes produced by the reference's own slow5lib (tests/golden/svb, made by
 tools/make_svbvec.py through oracle/_ref/ref_harness), and the round trip.  GPU: the device coder against the
-oracle on simulated batches, plus the decode round trip at full size."""
+oracle on simulated batches, plus the decode round trip at full size.  Natural signal has no three-byte value, no negative sample
+and no int16 wrap: test_injected_signals.py runs the device coder on arrays that do (slow5lib's golden arrays among them)."""
 import os
 import sys
 
