@@ -64,7 +64,8 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
     P.sig = Z.d_sig; P.sig_off = Z.d_sigoff; P.n_reads = n; P.n_chunks = n_chunks;
     P.L = cfg->chunk_len; P.S = cfg->stride; P.W = cfg->max_label;
     P.hist_max = CHUNK_HIST; P.one_wg_max = 1LL << 22;
-    // development build: 1 sends every read through the wide path (global histograms), 2 through the long one (several workgroups per read)
+    // development build: 1 sends every read through the wide path (global histograms), 2 through the long one (several workgroups per read);
+    // 3 leaves the statistics alone and makes k_chunk_labels divide in 64 bits, as it does for a read of 2^31 samples or more
     const int force = dev_env_int(SQG_DEV_ENV("SQG_TEST_CHUNK_GENERIC"), 0);
     if (force == 1) P.hist_max = 0;
     if (force == 2) P.one_wg_max = 0;
@@ -117,7 +118,7 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
         if (want_labels)
             hipLaunchKernelGGL(k_chunk_labels, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P, (const ReadDesc*)b->d_reads, (const uint8_t*)b->d_bases,
                                c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr, (int)c->cfg.profile.dwell_mean,
-                               (c->cfg.flags & SQG_RNA) ? 1 : 0, (c->cfg.flags & SQG_METH) ? 1 : 0, c->d_chunk_ev,
+                               (c->cfg.flags & SQG_RNA) ? 1 : 0, (c->cfg.flags & SQG_METH) ? 1 : 0, force == 3 ? 1 : 0, c->d_chunk_ev,
                                cfg->max_label > 0 ? out->labels : (uint8_t*)nullptr, out->label_len);
         HIPCHK(c, hipGetLastError());
     }

@@ -257,14 +257,14 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, const Re
 // generation-order sample) or e1 (which = 1: one past its last).  DNA: g = jS + which L; RNA: g = n - L + which L - jS.  All boundaries lie
 // in [0, n], so the interval is cut to that first and the divisions below see small non-negative numbers: 32-bit ones when the read allows
 // (64-bit division is a hundred instructions, and every event comes through here four times).
-struct ChunkGeom { long long n, nc, c0; int L, S, rna; };
+struct ChunkGeom { long long n, nc, c0; int L, S, rna; bool small; };   // small: n < 2^31, the divisions fit 32 bits
 __device__ static inline long long chunk_div(long long a, int S, bool small) {   // a >= 0
     return small ? (long long)((uint32_t)a / (uint32_t)S) : a / S;
 }
 __device__ static inline void chunk_mark(const ChunkGeom& G, int2* ev, long long lo, long long hi, int value) {
     lo = max(lo, -1LL); hi = min(hi, G.n);
     if (hi <= lo) return;
-    const bool small = G.n < (1LL << 31);
+    const bool small = G.small;
 #pragma unroll
     for (int which = 0; which < 2; which++) {
         // multiples jS in (a_lo, a_hi]
@@ -283,7 +283,7 @@ __device__ static inline uint32_t chunk_label_code(uint8_t b, int meth) { return
 // E[e], the first sample of event e, is the exclusive prefix sum of the read's dwells; the chunk boundaries in (E[e], E[e] + dwell[e]] belong
 // to event e + 1 (the first event that starts at or behind them), those at or before 0 to event 0, those behind the last start to n_events.
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const ReadDesc* __restrict__ reads, const uint8_t* __restrict__ bases,
-                                                           const uint16_t* __restrict__ dwell, int const_sps, int rna, int meth, int2* ev,
+                                                           const uint16_t* __restrict__ dwell, int const_sps, int rna, int meth, int div64, int2* ev,
                                                            uint8_t* labels, int* label_len) {
     __shared__ unsigned long long sh[8];
     const int r = blockIdx.x, t = threadIdx.x;
@@ -291,6 +291,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const 
     G.c0 = P.chunk_off[r]; G.nc = P.chunk_off[r + 1] - G.c0;
     if (G.nc <= 0) return;
     G.n = P.sig_off[r + 1] - P.sig_off[r]; G.L = P.L; G.S = P.S; G.rna = rna;
+    G.small = !div64 && G.n < (1LL << 31);                  // div64: the development build's test hook, the 64-bit divisions on every read
     const ReadDesc rd = reads[r];
     const int ne = rd.ne0;
     unsigned long long carry = 0;
