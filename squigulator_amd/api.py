@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h and include/sqg_chunks.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h and include/sqg_targets.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -104,6 +104,14 @@ class CChunkCfg(C.Structure):
 
 class CChunkOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("signal", "labels", "label_len", "chunk_read", "chunk_start", "med2", "mad4")]
+
+
+# include/sqg_targets.h: bound the same way
+EXPORTS_TARGETS = ["sqg_batch_chunk_targets"]
+
+
+class CChunkTargets(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("clean", "clean_raw", "moves", "kmer", "med2", "mad4")]
 
 
 class Chunks:
@@ -228,6 +236,9 @@ def load_library(path: str | None = None):
         L.sqg_chunk_plan.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(i64), C.POINTER(i64)]
         L.sqg_batch_chunks.restype = C.c_int
         L.sqg_batch_chunks.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
+    if all(hasattr(L, n) for n in EXPORTS_TARGETS):
+        L.sqg_batch_chunk_targets.restype = C.c_int
+        L.sqg_batch_chunk_targets.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
     _libs[path] = L
     return L
 
@@ -491,6 +502,36 @@ class Batch:
         torch.cuda.synchronize(dev)                         # (the allocator's pending work on these blocks, if any, before another stream writes them)
         self.gen._chk(self.gen.L.sqg_batch_chunks(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_chunks")
         return ch
+
+    def chunk_targets(self, chunk_len: int, stride: int | None = None, dtype="f16", norm="medmad", clean: bool = True,
+                      clean_raw: bool = False, moves: bool = True, kmer: bool = False, chunks: Chunks | None = None) -> Chunks:
+        """Per-sample targets for the chunks Batch.chunks() cuts with the same chunk_len / stride (sqg_batch_chunk_targets,
+        include/sqg_targets.h): torch tensors [n_chunks, L] on the batch's device -- clean (float16 / float32: the noise-free signal on
+        the noisy read's scale), clean_raw (int16: what --ideal-amp writes), moves (uint8: 1 where an event starts), kmer (uint32 bit
+        patterns in an int32 tensor: the pore-table row).  Those not asked for are None.  chunks=: a Chunks of this batch, whose med2 /
+        mad4 are passed in instead of being computed again."""
+        import torch
+        if not hasattr(self.gen.L, "sqg_batch_chunk_targets"):
+            raise SqgError(-1, "chunk_targets", "this backend has no sqg_batch_chunk_targets (include/sqg_targets.h)")
+        cfg = self._chunk_cfg(chunk_len, stride, 0, dtype, norm)
+        off, nc = self.chunk_plan(chunk_len, cfg.stride)
+        dev = torch.device("cuda", self.gen.device)
+        new = lambda want, dt: None if not want else (torch.zeros if nc == 0 else torch.empty)((nc, cfg.chunk_len), dtype=dt, device=dev)   # noqa: E731
+        tg = Chunks(n_chunks=nc, chunk_off=off, clean=new(clean, torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16),
+                    clean_raw=new(clean_raw, torch.int16), moves=new(moves, torch.uint8), kmer=new(kmer, torch.int32))
+        if nc == 0:
+            return tg
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None          # noqa: E731
+        st = (None, None)
+        if chunks is not None:
+            st = (getattr(chunks, "med2", None), getattr(chunks, "mad4", None))
+            for t in st:                                    # (a Chunks of another batch or device would silently put clean on a wrong scale)
+                if t is None or t.dtype != torch.int32 or t.device != dev or t.numel() != self.n_reads or not t.is_contiguous():
+                    raise SqgError(-1, "chunk_targets", f"chunks= must carry this batch's med2 / mad4: int32 [{self.n_reads}] on {dev}")
+        out = CChunkTargets(ptr(tg.clean), ptr(tg.clean_raw), ptr(tg.moves), ptr(tg.kmer), ptr(st[0]), ptr(st[1]))
+        torch.cuda.synchronize(dev)                         # (as in chunks(): the allocator's pending work on these blocks first)
+        self.gen._chk(self.gen.L.sqg_batch_chunk_targets(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_chunk_targets")
+        return tg
 
     def free(self):
         if self.handle:

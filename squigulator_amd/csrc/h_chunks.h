@@ -40,6 +40,26 @@ extern "C" int sqg_chunk_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_
     return SQG_OK;
 }
 
+// the statistics pass on the context's stream: every read's {median, 1 / (1.4826 MAD)} into P.consts, med2 / mad4 where P has them
+// (P.wide_list and P.ghist are the context's scratch; also run by sqg_batch_chunk_targets, h_targets.h)
+static int chunk_stats_run(sqg_ctx* c, sqg_batch* b, const ChunkParams& P) {
+    const hipStream_t st = c->stream;
+    const int n = b->n;
+    HIPCHK(c, hipMemsetAsync(c->d_chunk_wide, 0, sizeof(unsigned int), st));
+    hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
+    hipLaunchKernelGGL(k_chunk_stats_wide, dim3(CHUNK_WIDE_SLOTS), dim3(CHUNK_WG), 0, st, P);
+    for (int i = 0; i < n; i++) {
+        const long long ns = b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i];
+        if (ns <= 0 || ns <= P.one_wg_max) continue;
+        HIPCHK(c, hipMemsetAsync(c->d_chunk_ghist, 0, (size_t)2 * CHUNK_GBINS * sizeof(unsigned int), st));
+        const unsigned wgs = (unsigned)std::min<long long>((ns + 16 * CHUNK_WG - 1) / (16 * CHUNK_WG), 4LL * c->num_cu);
+        hipLaunchKernelGGL(k_chunk_hist_long, dim3(wgs), dim3(CHUNK_WG), 0, st, P, i);
+        hipLaunchKernelGGL(k_chunk_select_long, dim3(1), dim3(CHUNK_WG), 0, st, P, i);
+    }
+    HIPCHK(c, hipGetLastError());
+    return dbg_sync(c, "k_chunk_stats");
+}
+
 extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_t* cfg, const sqg_chunk_out_t* out) {
     int rc = chunk_check(c, b, cfg, "sqg_batch_chunks");
     if (rc) return rc;
@@ -87,21 +107,7 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
     HIPCHK(c, hipMemcpyAsync(c->d_chunk_off, off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     // pass 1, statistics: the read's constants for the emit kernel, med2 / mad4 for the caller
     const bool want_stats = out->med2 || out->mad4 || (out->signal && n_chunks > 0 && cfg->norm == SQG_CHUNK_MEDMAD);
-    if (want_stats) {
-        HIPCHK(c, hipMemsetAsync(c->d_chunk_wide, 0, sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
-        hipLaunchKernelGGL(k_chunk_stats_wide, dim3(CHUNK_WIDE_SLOTS), dim3(CHUNK_WG), 0, st, P);
-        for (int i = 0; i < n; i++) {
-            const long long ns = b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i];
-            if (ns <= 0 || ns <= P.one_wg_max) continue;
-            HIPCHK(c, hipMemsetAsync(c->d_chunk_ghist, 0, (size_t)2 * CHUNK_GBINS * sizeof(unsigned int), st));
-            const unsigned wgs = (unsigned)std::min<long long>((ns + 16 * CHUNK_WG - 1) / (16 * CHUNK_WG), 4LL * c->num_cu);
-            hipLaunchKernelGGL(k_chunk_hist_long, dim3(wgs), dim3(CHUNK_WG), 0, st, P, i);
-            hipLaunchKernelGGL(k_chunk_select_long, dim3(1), dim3(CHUNK_WG), 0, st, P, i);
-        }
-        HIPCHK(c, hipGetLastError());
-        if ((rc = dbg_sync(c, "k_chunk_stats"))) return rc;
-    }
+    if (want_stats && (rc = chunk_stats_run(c, b, P))) return rc;
     if (n_chunks > 0) {
         hipLaunchKernelGGL(k_chunk_index, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
         // pass 2, emit

@@ -219,6 +219,7 @@ struct sqg_ctx {
     unsigned int* d_chunk_wide = nullptr; size_t chunk_wide_cap = 0;
     unsigned int* d_chunk_ghist = nullptr; size_t chunk_ghist_cap = 0;
     std::vector<long long> h_chunk_off;
+    uint32_t* d_target_start = nullptr; size_t target_start_cap = 0;   // sqg_batch_chunk_targets (h_targets.h): first sample of every event within its read
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -3,6 +3,10 @@
 Per setting: the blocking call's wall-clock milliseconds (median of the timed calls, after a warm-up call), next to the same batch's
 generation time (sqg_timing_t.total_ms), and the bytes the call must move (2 N + dtype_bytes L n_chunks + W n_chunks) over that time,
 next to the streaming-store rate sqg_probe_store_bandwidth reports in the same run.  Prints a markdown table (profiles/chunks.md).
+Then the same for sqg_batch_chunk_targets (include/sqg_targets.h) on the same batch: clean + moves, all four outputs, each with and
+without the statistics of an earlier Batch.chunks passed in; bytes = what the call writes per sample (F16 clean 2, clean_raw 2, moves 1, kmer 4).  The milliseconds are the whole blocking
+Batch.chunk_targets call (tensor allocation, plan and synchronisation included); per-kernel times come from running this tool under
+tools/kstats.sh (profiles/chunk_targets.md).
 usage: python tools/chunks_rate.py [reads_per_batch=32768] [timed_calls=5] [genome_mb]"""
 import os
 import sys
@@ -54,5 +58,29 @@ for name, S, kw in (("L 4096, S = L, f16 medmad, W 512", L, {}), ("L 4096, S = L
     ms = float(np.median(ts[1:]))
     moved = 2 * N + (2 * L * nc if kw.get("signal", True) else 0) + (W * nc if kw.get("labels", True) else 0)
     print(f"| {name} | {nc} | {ms:.2f} (min {min(ts[1:]):.2f}, max {max(ts[1:]):.2f}) | {gen_ms:.2f} | {moved / 1e9:.2f} GB | {moved / ms / 1e6:.0f} | {moved / (ms * 1e-3) / store:.2f} |")
+
+print(f"\n# sqg_batch_chunk_targets on the same batch (L {L}, S = L, f16 medmad)\n")
+print("| outputs | statistics | chunks | call ms | bytes written | GB/s | of the store probe |")
+print("|---|---|---|---|---|---|---|")
+stats = b.chunks(L, L, 0, signal=False, labels=False)
+for name, per_sample, kw in (("clean + moves", 3, dict(clean=True, moves=True)), ("moves alone", 1, dict(clean=False, moves=True)),
+                             ("clean_raw alone", 2, dict(clean=False, moves=False, clean_raw=True)),
+                             ("clean, clean_raw, moves, kmer", 9, dict(clean=True, clean_raw=True, moves=True, kmer=True))):
+    for how, extra in (("computed by the call", {}), ("passed in", dict(chunks=stats))):
+        if not kw["clean"] and extra:
+            continue                                        # no clean: no statistics either way
+        ts = []
+        for it in range(REP + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tg = b.chunk_targets(L, L, **kw, **extra)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            nc = tg.n_chunks
+            del tg
+        ms = float(np.median(ts[1:]))
+        wrote = per_sample * L * nc
+        print(f"| {name} | {how if kw['clean'] else '-'} | {nc} | {ms:.2f} (min {min(ts[1:]):.2f}, max {max(ts[1:]):.2f}) | {wrote / 1e9:.2f} GB | "
+              f"{wrote / ms / 1e6:.0f} | {wrote / (ms * 1e-3) / store:.2f} |")
+del stats
 b.free()
 gen.close()
