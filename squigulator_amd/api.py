@@ -478,6 +478,20 @@ class Batch:
                       "sqg_chunk_plan")
         return off, int(nc.value)
 
+    def _chunk_job(self, chunk_len, stride, max_label, dtype, norm):
+        """what chunks() and chunk_targets() share: (cfg, chunk_off, n_chunks, device, new, call) -- new(shape, dtype): an output tensor;
+        call(name, out, *tensors): the C struct `out` filled with the tensors' addresses, then the library's `name` on this batch"""
+        import torch
+        cfg = self._chunk_cfg(chunk_len, stride, max_label, dtype, norm)
+        off, nc = self.chunk_plan(chunk_len, cfg.stride)
+        dev = torch.device("cuda", self.gen.device)
+        new = lambda shape, dt: (torch.zeros if nc == 0 else torch.empty)(shape, dtype=dt, device=dev)   # noqa: E731
+        def call(name, out, *tensors):
+            out = out(*(t.data_ptr() if t is not None and t.numel() else None for t in tensors))
+            torch.cuda.synchronize(dev)                     # (the allocator's pending work on these blocks, if any, before another stream writes them)
+            self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), name)
+        return cfg, off, nc, dev, new, call
+
     def chunks(self, chunk_len: int, stride: int | None = None, max_label: int = 0, dtype="f16", norm="medmad",
                signal: bool = True, labels: bool = True) -> Chunks:
         """Fixed-length, per-read normalised windows of the batch's signal and their base labels, made on the device
@@ -485,22 +499,15 @@ class Batch:
         label_len, chunk_read, chunk_start [n_chunks], med2, mad4 [n_reads].  signal=False / labels=False leave those passes out
         (the tensors are then None)."""
         import torch
-        cfg = self._chunk_cfg(chunk_len, stride, max_label, dtype, norm)
-        off, nc = self.chunk_plan(chunk_len, cfg.stride)
-        dev = torch.device("cuda", self.gen.device)
-        new = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev) if nc == 0 else torch.empty(shape, dtype=dt, device=dev)   # noqa: E731
+        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, max_label, dtype, norm)
         ch = Chunks(n_chunks=nc, chunk_off=off,
                     signal=new((nc, cfg.chunk_len), torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16) if signal else None,
                     labels=new((nc, cfg.max_label), torch.uint8) if labels else None,
                     label_len=new((nc,), torch.int32) if labels else None,
                     chunk_read=new((nc,), torch.int32), chunk_start=new((nc,), torch.int64),
                     med2=torch.zeros(self.n_reads, dtype=torch.int32, device=dev), mad4=torch.zeros(self.n_reads, dtype=torch.int32, device=dev))
-        if nc == 0:
-            return ch
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None          # noqa: E731
-        out = CChunkOut(ptr(ch.signal), ptr(ch.labels), ptr(ch.label_len), ptr(ch.chunk_read), ptr(ch.chunk_start), ptr(ch.med2), ptr(ch.mad4))
-        torch.cuda.synchronize(dev)                         # (the allocator's pending work on these blocks, if any, before another stream writes them)
-        self.gen._chk(self.gen.L.sqg_batch_chunks(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_chunks")
+        if nc:
+            call("sqg_batch_chunks", CChunkOut, ch.signal, ch.labels, ch.label_len, ch.chunk_read, ch.chunk_start, ch.med2, ch.mad4)
         return ch
 
     def chunk_targets(self, chunk_len: int, stride: int | None = None, dtype="f16", norm="medmad", clean: bool = True,
@@ -513,24 +520,19 @@ class Batch:
         import torch
         if not hasattr(self.gen.L, "sqg_batch_chunk_targets"):
             raise SqgError(-1, "chunk_targets", "this backend has no sqg_batch_chunk_targets (include/sqg_targets.h)")
-        cfg = self._chunk_cfg(chunk_len, stride, 0, dtype, norm)
-        off, nc = self.chunk_plan(chunk_len, cfg.stride)
-        dev = torch.device("cuda", self.gen.device)
-        new = lambda want, dt: None if not want else (torch.zeros if nc == 0 else torch.empty)((nc, cfg.chunk_len), dtype=dt, device=dev)   # noqa: E731
-        tg = Chunks(n_chunks=nc, chunk_off=off, clean=new(clean, torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16),
-                    clean_raw=new(clean_raw, torch.int16), moves=new(moves, torch.uint8), kmer=new(kmer, torch.int32))
+        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, 0, dtype, norm)
+        row = lambda want, dt: new((nc, cfg.chunk_len), dt) if want else None           # noqa: E731
+        tg = Chunks(n_chunks=nc, chunk_off=off, clean=row(clean, torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16),
+                    clean_raw=row(clean_raw, torch.int16), moves=row(moves, torch.uint8), kmer=row(kmer, torch.int32))
         if nc == 0:
             return tg
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None          # noqa: E731
         st = (None, None)
         if chunks is not None:
             st = (getattr(chunks, "med2", None), getattr(chunks, "mad4", None))
             for t in st:                                    # (a Chunks of another batch or device would silently put clean on a wrong scale)
                 if t is None or t.dtype != torch.int32 or t.device != dev or t.numel() != self.n_reads or not t.is_contiguous():
                     raise SqgError(-1, "chunk_targets", f"chunks= must carry this batch's med2 / mad4: int32 [{self.n_reads}] on {dev}")
-        out = CChunkTargets(ptr(tg.clean), ptr(tg.clean_raw), ptr(tg.moves), ptr(tg.kmer), ptr(st[0]), ptr(st[1]))
-        torch.cuda.synchronize(dev)                         # (as in chunks(): the allocator's pending work on these blocks first)
-        self.gen._chk(self.gen.L.sqg_batch_chunk_targets(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_chunk_targets")
+        call("sqg_batch_chunk_targets", CChunkTargets, tg.clean, tg.clean_raw, tg.moves, tg.kmer, *st)
         return tg
 
     def free(self):

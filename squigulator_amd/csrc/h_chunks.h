@@ -32,7 +32,7 @@ extern "C" int sqg_chunk_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_
     if (rc) return rc;
     if (!n_chunks) { c->err = "sqg_chunk_plan: n_chunks must not be NULL"; return SQG_EINVAL; }
     if ((rc = sqg_batch_wait(c, b, nullptr))) return rc;
-    std::vector<long long>& off = c->h_chunk_off;
+    std::vector<long long>& off = c->chunk.h_off;
     off.resize((size_t)b->n + 1);
     chunk_plan(b, cfg, off.data());
     if (chunk_off) for (int i = 0; i <= b->n; i++) chunk_off[i] = (int64_t)off[(size_t)i];
@@ -40,18 +40,64 @@ extern "C" int sqg_chunk_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_
     return SQG_OK;
 }
 
+// What sqg_batch_chunks and sqg_batch_chunk_targets (h_targets.h) share of one call
+struct ChunkJob {
+    const long long* plan = nullptr; long long n_chunks = 0;   // [n_reads+1] first chunk of every read (host: ChunkScratch::h_off)
+    ChunkParams P{};                                           // all but the caller's outputs
+    int force = 0; hipStream_t st = nullptr;                   // development build: SQG_TEST_CHUNK_GENERIC; the context's stream
+};
+
+// The shared opening of both calls, behind chunk_check and the caller's own argument checks: the batch still owns its device results (and
+// its dwell set, if need_dwell), it has finished, the plan, the parameters.  Host work only.  An empty batch leaves J->P.n_reads 0.
+static int chunk_begin(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, const char* who, bool need_dwell, ChunkJob* J) {
+    if (b->run_idx + 2 < c->runs || !slot_is_mine(c, b) || (need_dwell && !cset_is_mine(c, b))) {
+        c->err = std::string(who) + ": the batch's device results have been handed to a later batch";
+        return SQG_ESEQUENCE;
+    }
+    if (int rc = sqg_batch_wait(c, b, nullptr)) return rc;               // waits for the batch's own kernels; fills sig_off
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int n = b->n;
+    if (n == 0) return SQG_OK;
+    c->chunk.h_off.resize((size_t)n + 1);
+    chunk_plan(b, cfg, c->chunk.h_off.data());
+    J->plan = c->chunk.h_off.data(); J->n_chunks = J->plan[n]; J->st = c->stream;
+    ChunkParams& P = J->P;
+    P.sig = c->slot[b->slot].d_sig; P.sig_off = c->slot[b->slot].d_sigoff; P.n_reads = n; P.n_chunks = J->n_chunks;
+    P.L = cfg->chunk_len; P.S = cfg->stride; P.W = cfg->max_label;
+    // development build: 1 sends every read through the wide path (global histograms), 2 through the long one (several workgroups per read);
+    // 3 leaves the statistics alone and makes k_chunk_labels divide in 64 bits, as it does for a read of 2^31 samples or more
+    J->force = dev_env_int(SQG_DEV_ENV("SQG_TEST_CHUNK_GENERIC"), 0);
+    P.hist_max = J->force == 1 ? 0 : CHUNK_HIST; P.one_wg_max = J->force == 2 ? 0 : 1LL << 22;
+    P.range = c->cfg.profile.range; P.dig = c->cfg.profile.digitisation;
+    return SQG_OK;
+}
+
+// ... and the first device work of both: the scratch of the shared passes, the plan uploaded
+static int chunk_upload(sqg_ctx* c, ChunkJob* J) {
+    ChunkScratch& X = c->chunk;
+    const size_t n = (size_t)J->P.n_reads;
+    int rc;
+    if ((rc = ensure(c, (void**)&X.d_off, &X.off_cap, n + 1, sizeof(long long)))) return rc;
+    if ((rc = ensure(c, (void**)&X.d_const, &X.const_cap, n, sizeof(float2)))) return rc;
+    if ((rc = ensure(c, (void**)&X.d_wide, &X.wide_cap, n + 1, sizeof(unsigned int)))) return rc;
+    if ((rc = ensure(c, (void**)&X.d_ghist, &X.ghist_cap, (size_t)CHUNK_WIDE_SLOTS * 2 * CHUNK_GBINS, sizeof(unsigned int)))) return rc;
+    if ((rc = ensure(c, (void**)&X.d_read, &X.read_cap, (size_t)J->n_chunks + 1, sizeof(int)))) return rc;
+    J->P.chunk_off = X.d_off; J->P.consts = X.d_const; J->P.wide_list = X.d_wide; J->P.ghist = X.d_ghist; J->P.chunk_read = X.d_read;
+    HIPCHK(c, hipMemcpyAsync(X.d_off, J->plan, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, J->st));
+    return SQG_OK;
+}
+
 // the statistics pass on the context's stream: every read's {median, 1 / (1.4826 MAD)} into P.consts, med2 / mad4 where P has them
-// (P.wide_list and P.ghist are the context's scratch; also run by sqg_batch_chunk_targets, h_targets.h)
 static int chunk_stats_run(sqg_ctx* c, sqg_batch* b, const ChunkParams& P) {
     const hipStream_t st = c->stream;
     const int n = b->n;
-    HIPCHK(c, hipMemsetAsync(c->d_chunk_wide, 0, sizeof(unsigned int), st));
+    HIPCHK(c, hipMemsetAsync(P.wide_list, 0, sizeof(unsigned int), st));
     hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
     hipLaunchKernelGGL(k_chunk_stats_wide, dim3(CHUNK_WIDE_SLOTS), dim3(CHUNK_WG), 0, st, P);
     for (int i = 0; i < n; i++) {
         const long long ns = b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i];
         if (ns <= 0 || ns <= P.one_wg_max) continue;
-        HIPCHK(c, hipMemsetAsync(c->d_chunk_ghist, 0, (size_t)2 * CHUNK_GBINS * sizeof(unsigned int), st));
+        HIPCHK(c, hipMemsetAsync(P.ghist, 0, (size_t)2 * CHUNK_GBINS * sizeof(unsigned int), st));
         const unsigned wgs = (unsigned)std::min<long long>((ns + 16 * CHUNK_WG - 1) / (16 * CHUNK_WG), 4LL * c->num_cu);
         hipLaunchKernelGGL(k_chunk_hist_long, dim3(wgs), dim3(CHUNK_WG), 0, st, P, i);
         hipLaunchKernelGGL(k_chunk_select_long, dim3(1), dim3(CHUNK_WG), 0, st, P, i);
@@ -65,46 +111,17 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
     if (rc) return rc;
     if (!out) { c->err = "sqg_batch_chunks: out must not be NULL"; return SQG_EINVAL; }
     if (out->signal && ((uintptr_t)out->signal & 15)) { c->err = "sqg_batch_chunks: signal must be 16-byte aligned"; return SQG_EINVAL; }
-    const bool need_dwell = c->use_dwell_stream && (out->labels || out->label_len);
-    if (b->run_idx + 2 < c->runs || !slot_is_mine(c, b) || (need_dwell && !cset_is_mine(c, b))) {
-        c->err = "sqg_batch_chunks: the batch's device results have been handed to a later batch";
-        return SQG_ESEQUENCE;
-    }
-    if ((rc = sqg_batch_wait(c, b, nullptr))) return rc;                 // waits for the batch's own kernels; fills sig_off
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+    ChunkJob J;
+    if ((rc = chunk_begin(c, b, cfg, "sqg_batch_chunks", c->use_dwell_stream && (out->labels || out->label_len), &J)) || J.P.n_reads == 0) return rc;
+    if ((rc = chunk_upload(c, &J))) return rc;
+    const long long n_chunks = J.n_chunks;
     const int n = b->n;
-    if (n == 0) return SQG_OK;
-    sqg_ctx::Slot& Z = c->slot[b->slot];
-    std::vector<long long>& off = c->h_chunk_off;
-    off.resize((size_t)n + 1);
-    chunk_plan(b, cfg, off.data());
-    const long long n_chunks = off[(size_t)n];
-
-    ChunkParams P{};
-    P.sig = Z.d_sig; P.sig_off = Z.d_sigoff; P.n_reads = n; P.n_chunks = n_chunks;
-    P.L = cfg->chunk_len; P.S = cfg->stride; P.W = cfg->max_label;
-    P.hist_max = CHUNK_HIST; P.one_wg_max = 1LL << 22;
-    // development build: 1 sends every read through the wide path (global histograms), 2 through the long one (several workgroups per read);
-    // 3 leaves the statistics alone and makes k_chunk_labels divide in 64 bits, as it does for a read of 2^31 samples or more
-    const int force = dev_env_int(SQG_DEV_ENV("SQG_TEST_CHUNK_GENERIC"), 0);
-    if (force == 1) P.hist_max = 0;
-    if (force == 2) P.one_wg_max = 0;
+    const hipStream_t st = J.st;
+    ChunkParams& P = J.P;                                               // ... and the caller's outputs
     P.med2 = out->med2; P.mad4 = out->mad4;
     P.chunk_read_out = out->chunk_read; P.chunk_start_out = (long long*)out->chunk_start;
-    P.range = c->cfg.profile.range; P.dig = c->cfg.profile.digitisation;
-
-    if ((rc = ensure(c, (void**)&c->d_chunk_off, &c->chunk_off_cap, (size_t)n + 1, sizeof(long long)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_chunk_const, &c->chunk_const_cap, (size_t)n, sizeof(float2)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_chunk_wide, &c->chunk_wide_cap, (size_t)n + 1, sizeof(unsigned int)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_chunk_ghist, &c->chunk_ghist_cap, (size_t)CHUNK_WIDE_SLOTS * 2 * CHUNK_GBINS, sizeof(unsigned int)))) return rc;
-    if ((rc = ensure(c, (void**)&c->d_chunk_read, &c->chunk_read_cap, (size_t)n_chunks + 1, sizeof(int)))) return rc;
     const bool want_labels = n_chunks > 0 && ((out->labels && cfg->max_label > 0) || out->label_len);
-    if (want_labels && (rc = ensure(c, (void**)&c->d_chunk_ev, &c->chunk_ev_cap, (size_t)n_chunks, sizeof(int2)))) return rc;
-    P.chunk_off = c->d_chunk_off; P.consts = c->d_chunk_const; P.wide_list = c->d_chunk_wide; P.ghist = c->d_chunk_ghist;
-    P.chunk_read = c->d_chunk_read;
-
-    const hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->d_chunk_off, off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (want_labels && (rc = ensure(c, (void**)&c->chunk.d_ev, &c->chunk.ev_cap, (size_t)n_chunks, sizeof(int2)))) return rc;
     // pass 1, statistics: the read's constants for the emit kernel, med2 / mad4 for the caller
     const bool want_stats = out->med2 || out->mad4 || (out->signal && n_chunks > 0 && cfg->norm == SQG_CHUNK_MEDMAD);
     if (want_stats && (rc = chunk_stats_run(c, b, P))) return rc;
@@ -112,7 +129,7 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
         hipLaunchKernelGGL(k_chunk_index, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
         // pass 2, emit
         if (out->signal) {
-            const int g8 = P.L >> 3, cpb = g8 >= CHUNK_WG ? 1 : CHUNK_WG / g8;
+            const int cpb = chunk_emit_geom(P.L).cpb;
             const unsigned wgs = (unsigned)std::min<long long>((n_chunks + cpb - 1) / cpb, 1LL << 20);
             const bool f32 = cfg->dtype == SQG_CHUNK_F32, pa = cfg->norm == SQG_CHUNK_PA;
 #define CHUNK_EMIT(F, A) hipLaunchKernelGGL((k_chunk_emit<F, A>), dim3(wgs), dim3(CHUNK_WG), 0, st, P, (const ReadDesc*)b->d_reads, out->signal)
@@ -124,7 +141,7 @@ extern "C" int sqg_batch_chunks(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cf
         if (want_labels)
             hipLaunchKernelGGL(k_chunk_labels, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P, (const ReadDesc*)b->d_reads, (const uint8_t*)b->d_bases,
                                c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr, (int)c->cfg.profile.dwell_mean,
-                               (c->cfg.flags & SQG_RNA) ? 1 : 0, (c->cfg.flags & SQG_METH) ? 1 : 0, force == 3 ? 1 : 0, c->d_chunk_ev,
+                               (c->cfg.flags & SQG_RNA) ? 1 : 0, (c->cfg.flags & SQG_METH) ? 1 : 0, J.force == 3 ? 1 : 0, c->chunk.d_ev,
                                cfg->max_label > 0 ? out->labels : (uint8_t*)nullptr, out->label_len);
         HIPCHK(c, hipGetLastError());
     }

@@ -76,6 +76,19 @@ struct HostPool {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+// device scratch of sqg_batch_chunks and sqg_batch_chunk_targets, grown by ensure(); the calls of a context share it (they block)
+struct ChunkScratch {
+    long long* d_off = nullptr; size_t off_cap = 0; std::vector<long long> h_off;   // [n_reads+1] first chunk of every read, device and host
+    float2* d_const = nullptr; size_t const_cap = 0;           // [n_reads] {median, 1 / (1.4826 MAD)}
+    int* d_read = nullptr; size_t read_cap = 0;                // [n_chunks] chunk -> read
+    int2* d_ev = nullptr; size_t ev_cap = 0;                   // [n_chunks] every chunk's event range (k_chunk_labels)
+    unsigned int* d_wide = nullptr; size_t wide_cap = 0;       // the list of reads whose codes span more than the LDS histogram
+    unsigned int* d_ghist = nullptr; size_t ghist_cap = 0;     // the global histograms of the generic statistics paths
+    uint32_t* d_start = nullptr; size_t start_cap = 0;         // [n_events] first sample of every event within its read (k_target_scan)
+    void release() { for (void* p : {(void*)d_off, (void*)d_const, (void*)d_read, (void*)d_ev, (void*)d_wide, (void*)d_ghist, (void*)d_start}) (void)hipFree(p);
+                     *this = ChunkScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -210,16 +223,7 @@ struct sqg_ctx {
     // (profiles/r05_summary.md); the first large batches of a context time the pass itself on three more allocations per slot and keep the best
     int cal_runs_left = 12;
     void* b5_reader = nullptr; int b5_reader_buf = -1; void (*b5_reader_drain)(void* writer, bool unbind) = nullptr;
-    // sqg_batch_chunks (h_chunks.h): first chunk of every read, the reads' {median, 1 / (1.4826 MAD)}, chunk -> read, every chunk's event range,
-    // the list of reads whose codes span more than the LDS histogram, the global histograms of the generic statistics paths
-    long long* d_chunk_off = nullptr; size_t chunk_off_cap = 0;
-    float2* d_chunk_const = nullptr; size_t chunk_const_cap = 0;
-    int* d_chunk_read = nullptr; size_t chunk_read_cap = 0;
-    int2* d_chunk_ev = nullptr; size_t chunk_ev_cap = 0;
-    unsigned int* d_chunk_wide = nullptr; size_t chunk_wide_cap = 0;
-    unsigned int* d_chunk_ghist = nullptr; size_t chunk_ghist_cap = 0;
-    std::vector<long long> h_chunk_off;
-    uint32_t* d_target_start = nullptr; size_t target_start_cap = 0;   // sqg_batch_chunk_targets (h_targets.h): first sample of every event within its read
+    ChunkScratch chunk;                                        // sqg_batch_chunks, sqg_batch_chunk_targets (h_chunks.h, h_targets.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

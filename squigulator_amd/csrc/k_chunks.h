@@ -6,6 +6,7 @@
 //                        bins go on a list, reads longer than the caller's limit are left to the long path
 //   k_chunk_stats_wide   the listed reads: a 65536-bin histogram in global memory per workgroup, same selection
 //   k_chunk_hist_long, k_chunk_select_long   one long read over many workgroups: global histogram, then the selection by one workgroup
+//   k_chunk_consts       the same constants from med2 / mad4 the caller passed in (sqg_batch_chunk_targets with the statistics of an earlier call)
 //   k_chunk_index        chunk -> read, chunk -> first sample
 //   k_chunk_emit         streaming: 2 B/sample in, the chunk rows out in 16-byte stores
 //   k_chunk_labels       one workgroup per read: one scan of its dwells finds every chunk's event range [e0, e1); then the codes
@@ -188,6 +189,11 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_select_long(ChunkParams P, i
     if (threadIdx.x == 0) chunk_write_stats(P, r, med2, mad4);
 }
 
+__global__ __launch_bounds__(CHUNK_WG) void k_chunk_consts(ChunkParams P, const int* __restrict__ med2, const int* __restrict__ mad4) {
+    const int r = blockIdx.x * CHUNK_WG + threadIdx.x;
+    if (r < P.n_reads) chunk_write_stats(P, r, med2[r], mad4[r]);              // (P.med2 / P.mad4 are null: only the constants are written)
+}
+
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_index(ChunkParams P) {
     const int r = blockIdx.x;
     const long long c0 = P.chunk_off[r], nc = P.chunk_off[r + 1] - c0;
@@ -205,13 +211,33 @@ __device__ static inline unsigned int chunk_f16_bits(float x) {
     const _Float16 h = (_Float16)x;                        // v_cvt_f16_f32: round to nearest even, subnormals kept
     return (unsigned int)__builtin_bit_cast(unsigned short, h);
 }
+// the two normalisations of a code (include/sqg_chunks.h); cs: the read's {median, 1 / (1.4826 MAD)}
+__device__ static inline float chunk_norm_medmad(int raw, float2 cs) { return ((float)raw - cs.x) * cs.y; }
+__device__ static inline float chunk_norm_pa(int raw, double offset, double range, double dig) { return (float)((((double)raw + offset) * range) / dig); }
+// 8 consecutive values of a row to out[at ..] (elements; 16-byte aligned): two 16-byte stores of fp32, or one of fp16 (rounded from the fp32 value)
+template <bool F32>
+__device__ static inline void chunk_store8(void* out, long long at, const float (&x)[8]) {
+    if (F32) {
+        float4* o = reinterpret_cast<float4*>(static_cast<float*>(out) + at);
+        o[0] = make_float4(x[0], x[1], x[2], x[3]);
+        o[1] = make_float4(x[4], x[5], x[6], x[7]);
+    } else {
+        uint4 v;
+        v.x = chunk_f16_bits(x[0]) | (chunk_f16_bits(x[1]) << 16); v.y = chunk_f16_bits(x[2]) | (chunk_f16_bits(x[3]) << 16);
+        v.z = chunk_f16_bits(x[4]) | (chunk_f16_bits(x[5]) << 16); v.w = chunk_f16_bits(x[6]) | (chunk_f16_bits(x[7]) << 16);
+        *reinterpret_cast<uint4*>(static_cast<unsigned short*>(out) + at) = v;
+    }
+}
+
+// k_chunk_emit's split of a workgroup, for the kernel and for the host that sizes its grid: g8 threads per chunk, cpb chunks at a time
+struct ChunkEmitGeom { int g8, cpb; };
+__host__ __device__ static inline ChunkEmitGeom chunk_emit_geom(int L) { return {L >> 3, (L >> 3) >= CHUNK_WG ? 1 : CHUNK_WG / (L >> 3)}; }
 
 // A workgroup takes 256 / (L / 8) chunks at a time (one for L >= 2048); a thread 8 consecutive samples: 20 bytes in (the read starts at
 // any 2-byte address), 16 or 32 bytes out.  offset: the reads' slow5 offsets (PA), from the batch's descriptors.
 template <bool F32, bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, const ReadDesc* __restrict__ reads, void* __restrict__ out) {
-    const int g8 = P.L >> 3;
-    const int cpb = g8 >= CHUNK_WG ? 1 : CHUNK_WG / g8;
+    const auto [g8, cpb] = chunk_emit_geom(P.L);
     const int sub = (int)threadIdx.x / g8, w0 = (int)threadIdx.x - sub * g8;
     if (sub >= cpb) return;
     for (long long c = (long long)blockIdx.x * cpb + sub; c < P.n_chunks; c += (long long)gridDim.x * cpb) {
@@ -235,20 +261,9 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, const Re
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int raw = (int)(int16_t)((a[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-                if (PA) x[i] = (float)((((double)raw + offset) * P.range) / P.dig);
-                else x[i] = ((float)raw - cs.x) * cs.y;
+                x[i] = PA ? chunk_norm_pa(raw, offset, P.range, P.dig) : chunk_norm_medmad(raw, cs);
             }
-            const long long at = c * (long long)P.L + (long long)w * 8;
-            if (F32) {
-                float4* o = reinterpret_cast<float4*>(static_cast<float*>(out) + at);
-                o[0] = make_float4(x[0], x[1], x[2], x[3]);
-                o[1] = make_float4(x[4], x[5], x[6], x[7]);
-            } else {
-                uint4 v;
-                v.x = chunk_f16_bits(x[0]) | (chunk_f16_bits(x[1]) << 16); v.y = chunk_f16_bits(x[2]) | (chunk_f16_bits(x[3]) << 16);
-                v.z = chunk_f16_bits(x[4]) | (chunk_f16_bits(x[5]) << 16); v.w = chunk_f16_bits(x[6]) | (chunk_f16_bits(x[7]) << 16);
-                *reinterpret_cast<uint4*>(static_cast<unsigned short*>(out) + at) = v;
-            }
+            chunk_store8<F32>(out, c * (long long)P.L + (long long)w * 8, x);
         }
     }
 }
@@ -280,8 +295,31 @@ __device__ static inline void chunk_mark(const ChunkGeom& G, int2* ev, long long
 
 __device__ static inline uint32_t chunk_label_code(uint8_t b, int meth) { return (meth && b == 'M') ? 5u : base_code(b) + 1u; }
 
-// E[e], the first sample of event e, is the exclusive prefix sum of the read's dwells; the chunk boundaries in (E[e], E[e] + dwell[e]] belong
-// to event e + 1 (the first event that starts at or behind them), those at or before 0 to event 0, those behind the last start to n_events.
+// E[e], the first sample of event e relative to its read, is the exclusive prefix sum of the read's dwells.  f(e, E[e], dwell[e]) for every
+// event of read rd, the whole workgroup calling: 4 consecutive events per thread, tiles of 4 * CHUNK_WG events, the sum carried from tile
+// to tile.  dwell == nullptr: a constant-dwell context, every dwell is const_sps.  sh: the 8 words of chunk_scan_excl.
+template <class F>
+__device__ static inline void chunk_for_event_starts(const ReadDesc& rd, const uint16_t* dwell, int const_sps, unsigned long long* sh, F f) {
+    const int ne = rd.ne0, t = threadIdx.x;
+    unsigned long long carry = 0;
+    for (int base = 0; base < ne; base += 4 * CHUNK_WG) {
+        const int e0 = base + 4 * t;
+        int d[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (dwell ? (int)dwell[rd.ev_off + e0 + q] : const_sps) : 0;
+        unsigned long long total;
+        unsigned long long E = carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total);
+        carry += total;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (e0 + q < ne) f(e0 + q, E, d[q]);
+            E += (unsigned long long)d[q];
+        }
+    }
+}
+
+// The chunk boundaries in (E[e], E[e] + dwell[e]] belong to event e + 1 (the first event that starts at or behind them), those at or before 0
+// to event 0, those behind the last start to n_events.
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const ReadDesc* __restrict__ reads, const uint8_t* __restrict__ bases,
                                                            const uint16_t* __restrict__ dwell, int const_sps, int rna, int meth, int div64, int2* ev,
                                                            uint8_t* labels, int* label_len) {
@@ -294,25 +332,10 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const 
     G.small = !div64 && G.n < (1LL << 31);                  // div64: the development build's test hook, the 64-bit divisions on every read
     const ReadDesc rd = reads[r];
     const int ne = rd.ne0;
-    unsigned long long carry = 0;
-    for (int base = 0; base < ne; base += 4 * CHUNK_WG) {
-        const int e0 = base + 4 * t;
-        int d[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (dwell ? (int)dwell[rd.ev_off + e0 + q] : const_sps) : 0;
-        unsigned long long total;
-        long long E = (long long)(carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total));
-        carry += total;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int e = e0 + q;
-            if (e < ne) {
-                if (e == 0) chunk_mark(G, ev, -CHUNK_BIG, 0, 0);
-                chunk_mark(G, ev, E, e == ne - 1 ? CHUNK_BIG : E + d[q], e + 1);
-            }
-            E += d[q];
-        }
-    }
+    chunk_for_event_starts(rd, dwell, const_sps, sh, [&, ne](int e, long long E, int d) {
+        if (e == 0) chunk_mark(G, ev, -CHUNK_BIG, 0, 0);
+        chunk_mark(G, ev, E, e == ne - 1 ? CHUNK_BIG : E + d, e + 1);
+    });
     __threadfence();
     __syncthreads();
     const int lane = t & 63;

@@ -2,8 +2,7 @@
 // Part of the device code of the per-read signal path; included through sqg_kernels.h (see there for the overview).
 //
 //   k_target_scan    pass A, one workgroup per read: ev_start[e] = E[e], the first generation-order sample of event e, relative to the read
-//                    (a segmented exclusive scan of the dwells).  Not run in constant-dwell contexts, where E[e] = e * sps.
-//   k_target_consts  {median, 1 / (1.4826 MAD)} of every read from med2 / mad4 the caller passed in (else k_chunk_stats makes them)
+//                    (chunk_for_event_starts, k_chunks.h: the scan k_chunk_labels runs).  Not run in constant-dwell contexts, where E[e] = e * sps.
 //   k_target_emit    pass B, streaming: writes up to 9 B per sample and reads next to nothing.  A workgroup takes TGT_TILE generation-order
 //                    samples of one chunk at a time (or 256 / (L / 16) whole chunks when L is smaller), a thread 16 consecutive ones:
 //                      1. the first event that starts in the tile: one search over ev_start, eight probes a round (their loads in flight
@@ -34,30 +33,20 @@ struct TargetParams {
 __global__ __launch_bounds__(CHUNK_WG) void k_target_scan(ChunkParams P, const ReadDesc* __restrict__ reads, const uint16_t* __restrict__ dwell,
                                                           uint32_t* __restrict__ ev_start) {
     __shared__ unsigned long long sh[8];
-    const int r = blockIdx.x, t = threadIdx.x;
+    const int r = blockIdx.x;
     if (P.chunk_off[r + 1] == P.chunk_off[r]) return;       // no chunk asks for this read's events
     const ReadDesc rd = reads[r];
-    const int ne = rd.ne0;
-    unsigned long long carry = 0;
-    for (int base = 0; base < ne; base += 4 * CHUNK_WG) {
-        const int e0 = base + 4 * t;
-        int d[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (int)dwell[rd.ev_off + e0 + q] : 0;
-        unsigned long long total;
-        unsigned long long E = carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total);
-        carry += total;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (e0 + q < ne) ev_start[rd.ev_off + e0 + q] = (uint32_t)E;      // (the host has checked: the read has at most UINT32_MAX samples)
-            E += (unsigned long long)d[q];
-        }
-    }
+    __builtin_assume(dwell != nullptr);                     // (the host launches this pass in dwell-stream contexts only)
+    chunk_for_event_starts(rd, dwell, 0, sh, [&](int e, unsigned long long E, int) {
+        ev_start[rd.ev_off + e] = (uint32_t)E;              // (the host has checked: the read has at most UINT32_MAX samples)
+    });
 }
 
-__global__ __launch_bounds__(CHUNK_WG) void k_target_consts(ChunkParams P, const int* __restrict__ med2, const int* __restrict__ mad4) {
-    const int r = blockIdx.x * CHUNK_WG + threadIdx.x;
-    if (r < P.n_reads) chunk_write_stats(P, r, med2[r], mad4[r]);              // (P.med2 / P.mad4 are null: only the constants are written)
+// k_target_emit's split of its work, for the kernel and the host that sizes its grid: tiles per chunk, threads per tile, tiles of a workgroup at a time
+struct TargetGeom { int n_tiles, tpc, cpb; };
+__host__ __device__ static inline TargetGeom tgt_geom(int L) {
+    const int tpc = ((L < TGT_TILE ? L : TGT_TILE) + TGT_SPT - 1) / TGT_SPT;
+    return {(L + TGT_TILE - 1) / TGT_TILE, tpc, CHUNK_WG / tpc};
 }
 
 // the first e in [0, ne) with E[e] >= g, ne if there is none.  E ascends.  Eight probes a round cut [lo, hi] to less than an eighth.
@@ -92,9 +81,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
     __shared__ int ev_code[RAW ? EV_N : 1];
     __shared__ float ev_x[CLEAN != 0 ? EV_N : 1];
     const int t = threadIdx.x;
-    const int n_tiles = (P.L + TGT_TILE - 1) / TGT_TILE;
-    const int tpc = (min(P.L, TGT_TILE) + TGT_SPT - 1) / TGT_SPT;             // threads per chunk (or tile of a chunk)
-    const int cpb = CHUNK_WG / tpc;
+    const auto [n_tiles, tpc, cpb] = tgt_geom(P.L);
     const int sub = t / tpc, w0 = t - sub * tpc;
     const long long n_items = P.n_chunks * n_tiles;
     for (long long base = (long long)blockIdx.x * cpb; base < n_items; base += (long long)gridDim.x * cpb) {
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
                     if (CLEAN != 0 || RAW) {
                         const int code = (int)to_i16((double)T.model[rank].x * P.dig / P.range - offset);      // src/gensig.c:270
                         if (RAW) ev_code[at] = code;
-                        if (CLEAN != 0) ev_x[at] = PA ? (float)((((double)code + offset) * P.range) / P.dig) : ((float)code - cs.x) * cs.y;
+                        if (CLEAN != 0) ev_x[at] = PA ? chunk_norm_pa(code, offset, P.range, P.dig) : chunk_norm_medmad(code, cs);
                     }
                 }
             }
@@ -190,18 +177,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
                     o[0] = make_uint4(kk[0], kk[1], kk[2], kk[3]);
                     o[1] = make_uint4(kk[4], kk[5], kk[6], kk[7]);
                 }
-                if (CLEAN != 0) {
-                    if (F32) {
-                        float4* o = reinterpret_cast<float4*>(static_cast<float*>(T.clean) + at);
-                        o[0] = make_float4(xx[0], xx[1], xx[2], xx[3]);
-                        o[1] = make_float4(xx[4], xx[5], xx[6], xx[7]);
-                    } else {
-                        uint4 v;
-                        v.x = chunk_f16_bits(xx[0]) | (chunk_f16_bits(xx[1]) << 16); v.y = chunk_f16_bits(xx[2]) | (chunk_f16_bits(xx[3]) << 16);
-                        v.z = chunk_f16_bits(xx[4]) | (chunk_f16_bits(xx[5]) << 16); v.w = chunk_f16_bits(xx[6]) | (chunk_f16_bits(xx[7]) << 16);
-                        *reinterpret_cast<uint4*>(static_cast<unsigned short*>(T.clean) + at) = v;
-                    }
-                }
+                if (CLEAN != 0) chunk_store8<F32>(T.clean, at, xx);
             }
         }
         if (MOVES) {

@@ -14,8 +14,8 @@
 //   k_svb_*       slow5lib's svb-zd signal compression                    (slow5lib/src/slow5_press.c:1055-1087)
 //   k_blow5_frame BLOW5 records (slow5_rec_to_mem's layout) in stored-block zlib streams (slow5lib/src/slow5.c:3928-4072)
 //   k_blow5_huff_* the same records in streams of two dynamic-Huffman blocks (SQG_BLOW5_HUFFMAN; codes built by kh_huff.h)
-//   k_chunk_*     per-read median / MAD, normalised fixed-length chunks and their base labels (include/sqg_chunks.h)
-//   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h)
+//   k_chunk_*     per-read median / MAD (or the constants from statistics passed in), normalised fixed-length chunks and their base labels (include/sqg_chunks.h)
+//   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
 // (src/rand.h:87-94).  CERTIFIED: a draw is first evaluated with fp32 hardware transcendentals;

@@ -15,8 +15,8 @@ import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch
 import chunks_ref as R
 import label_cases as LC
 import orc
+from chunk_support import _assert_equal
 from squigulator_amd import api, build, model, profiles
-from test_chunks import _assert_equal
 
 INPUTS = os.path.join(os.path.dirname(__file__), "golden", "inputs")
 NCOV = os.path.join(INPUTS, "nCoV-2019.reference.fasta")

@@ -4,7 +4,6 @@ same reads in an SQG_IDEAL_AMP context (HIP library and oracle).  Every comparis
 import ctypes as C
 import dataclasses
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -15,9 +14,9 @@ import chunks_ref as R
 import label_cases as LC
 import orc
 import targets_ref as T
+from chunk_support import ALL_SETTINGS, CASES, _context, _declared, _fixture_reads
 from refvec_cases import REFVEC_CASES
 from squigulator_amd import api, build, model, options, profiles
-from test_chunks import ALL_SETTINGS, CASES, _context, _fixture_reads
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VEC = os.path.join(ROOT, "tests", "golden", "refvec")
@@ -26,12 +25,6 @@ KEYS = ("clean", "clean_raw", "moves", "kmer")
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(sqg_[a-z0-9_]+)\s*\(", hdr))
-
-
 def test_header_declares_the_target_export_and_the_libraries_have_it():
     assert _declared("sqg_targets.h") == set(api.EXPORTS_TARGETS) == {"sqg_batch_chunk_targets"}
     assert _declared("sqg_chunks.h") == set(api.EXPORTS_CHUNKS) == {"sqg_chunk_plan", "sqg_batch_chunks"}
@@ -201,7 +194,7 @@ TWINS = {  # name -> (profile, extra flags, workers, how the reads are made)
 @pytest.mark.parametrize("name", list(TWINS))
 def test_clean_raw_is_the_signal_of_an_ideal_amp_twin(name):
     """same reads, seed and workers through a second context with SQG_IDEAL_AMP -- on the HIP library and on the oracle: its signal, cut by
-    the plan, is clean_raw"""
+    the plan, is clean_raw; and its PA chunks are the PA clean rows, bit for bit"""
     pname, extra, workers, how = TWINS[name]
     prof, fl = profiles.get_profile(pname)
     fl |= extra
@@ -228,6 +221,7 @@ def test_clean_raw_is_the_signal_of_an_ideal_amp_twin(name):
     np.testing.assert_array_equal(twin.signal(), np.concatenate([w.sig for w in want]), err_msg="the twin context against the oracle")
     assert not np.array_equal(b.signal(), twin.signal())
     np.testing.assert_array_equal(b.dwell(), twin.dwell())
+    np.testing.assert_array_equal(np.array(b.offset), np.array(twin.offset), err_msg="the twin draws the same offsets")
     tsig = twin.signal()
     tsigs = [tsig[twin.sig_off[i]:twin.sig_off[i + 1]] for i in range(twin.n_reads)]
     for L, S in ((256, 128), (64, 8), (72, 200)):
@@ -236,6 +230,9 @@ def test_clean_raw_is_the_signal_of_an_ideal_amp_twin(name):
         np.testing.assert_array_equal(_cpu(tg.clean_raw, "clean_raw"), _cut(tsigs, tg.chunk_off, L, S), err_msg=f"{name} L {L} S {S}: HIP twin")
         np.testing.assert_array_equal(_cpu(tg.clean_raw, "clean_raw"), _cut([w.sig for w in want], tg.chunk_off, L, S), err_msg=f"{name} L {L} S {S}: oracle")
         _invariants(b, tg, L, S, rna, f"{name} L {L} S {S}")
+        for d in ("f16", "f32"):                            # PA is a function of code and offset alone, one statement of it: clean IS the twin's noisy chunk
+            clean = b.chunk_targets(L, S, dtype=d, norm="pa", clean=True, moves=False).clean.cpu().numpy()
+            np.testing.assert_array_equal(R.bits(clean), R.bits(twin.chunks(L, S, 0, dtype=d, norm="pa", labels=False).signal.cpu().numpy()), err_msg=f"{name} L {L} S {S} {d}: PA clean")
     for x in (b, twin):
         x.free()
     for g in gens:

@@ -3,7 +3,6 @@ rules (chunks_ref.py) -- applied to the compiled reference's committed vectors, 
 results.  Every comparison is bit for bit (floats as integers)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -11,21 +10,14 @@ import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch
 
 import chunks_ref as R
 import orc
-from refvec_cases import LIVE_CMD, LIVE_SEEDS, REFVEC_CASES
-from squigulator_amd import api, build, model, options, profiles
+from chunk_support import ALL_SETTINGS, CASES, _assert_equal, _context, _cpu, _declared, _fixture_reads
+from refvec_cases import REFVEC_CASES
+from squigulator_amd import api, build, model, profiles
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-VEC = os.path.join(ROOT, "tests", "golden", "refvec")
-CASES = [(cid, cmd) for cid, cmd in REFVEC_CASES if "--prefix" not in cmd] + [(f"live_seed{s}", LIVE_CMD.format(seed=s)) for s in LIVE_SEEDS]
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(sqg_[a-z0-9_]+)\s*\(", hdr))
-
-
 def test_header_declares_the_chunk_exports_and_the_library_has_them():
     assert _declared("sqg_chunks.h") == set(api.EXPORTS_CHUNKS) == {"sqg_chunk_plan", "sqg_batch_chunks"}
     assert _declared("sqg.h") == set(api.EXPORTS)                      # the surface every backend implements is unchanged
@@ -112,41 +104,6 @@ def test_plan_arithmetic():
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU
-def _fixture_reads(cid):
-    v = np.load(os.path.join(VEC, cid + ".npz"))
-    meta = v["meta"]
-    so = go = eo = 0
-    out = []
-    for i in range(len(meta)):
-        rlen, nsig, nss = int(meta[i][4]), int(meta[i][7]), int(meta[i][8])
-        out.append(dict(seq=v["seq"][so:so + rlen].tobytes(), sig=v["sig"][go:go + nsig], ss=v["ss"][eo:eo + nss], offset=float(v["offset"][i])))
-        so += rlen; go += nsig; eo += nss
-    return out
-
-
-def _context(cmd, mode):
-    o = options.parse_args(cmd)
-    k = o.kmer_size_default
-    mean, stdv = model.synthetic_model(k, meth=bool(o.meth_freq))
-    gen = api.SignalGenerator(o.profile, o.flags, k, mean, stdv, o.seed, num_workers=o.threads, amp_noise=o.amp_noise, mode=mode)
-    return o, k, gen
-
-
-def _cpu(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def _assert_equal(ch, want, what, keys=("signal", "labels", "label_len", "chunk_read", "chunk_start", "med2", "mad4")):
-    assert ch.n_chunks == len(want["chunk_read"]), f"{what}: {ch.n_chunks} chunks, expected {len(want['chunk_read'])}"
-    np.testing.assert_array_equal(ch.chunk_off, want["chunk_off"], err_msg=f"{what}: chunk_off")
-    for key in keys:
-        got = _cpu(getattr(ch, key))
-        if got is None:
-            continue
-        assert got.shape == want[key].shape and got.dtype == want[key].dtype, f"{what}: {key} {got.shape} {got.dtype} vs {want[key].shape} {want[key].dtype}"
-        np.testing.assert_array_equal(R.bits(got), R.bits(want[key]), err_msg=f"{what}: {key}")
-
-
 def _run_case(cid, cmd, mode, settings, L=2048, S=1024, W=256, check_cover=True):
     """the case's reads through the HIP path batch by batch, Batch.chunks against chunks_ref over the FIXTURE's sig / ss / seq"""
     reads = _fixture_reads(cid)
@@ -167,9 +124,6 @@ def _run_case(cid, cmd, mode, settings, L=2048, S=1024, W=256, check_cover=True)
     if check_cover:
         assert with_chunk >= 0.9 * len(reads), f"{cid}: only {with_chunk} of {len(reads)} reads have a chunk"
         assert n_max_label <= W, f"{cid}: a chunk has {n_max_label} bases, W = {W}"
-
-
-ALL_SETTINGS = [("f16", "medmad"), ("f32", "medmad"), ("f16", "pa"), ("f32", "pa")]
 
 
 @pytest.mark.gpu

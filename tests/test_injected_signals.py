@@ -19,7 +19,7 @@ import signal_cases as SC
 from squigulator_amd import api, build, model, profiles
 from test_blow5 import parse_blow5
 from test_blow5_huffman import huffman_records
-import test_chunks as TC
+import chunk_support as TC
 
 ALL_SETTINGS, _assert_equal, _cpu = TC.ALL_SETTINGS, TC._assert_equal, TC._cpu
 
