@@ -123,24 +123,25 @@ def test_short_and_odd_reads():
     gen.close(); orac.close()
 
 
-def test_worker_shards_equal_one_context():
-    """Multi-GPU sharding at the C ABI: two contexts owning workers [0,5) and [5,12) (as two GPUs would)
-    reproduce, read for read, what one context owning all 12 workers produces -- over two batches."""
+def _worker_shards_equal_one_context(name, k, letters, sflags=0):
     import orc
-    from squigulator_amd import model, profiles, shard
-    prof, fl = profiles.get_profile("dna-r10-prom")
-    k = 9
-    mean, stdv = model.synthetic_model(k)
+    from squigulator_amd import model, profiles
+    prof, fl = profiles.get_profile(name)
+    fl |= sflags
+    mean, stdv = model.synthetic_model(k, meth=bool(sflags & profiles.SQ_METH))
     rng = np.random.default_rng(5)
     T = 12
-    batches = [[bytes(rng.choice(list(b"ACGT"), size=int(n)).astype(np.uint8)) for n in rng.integers(300, 1500, size=T)]
+    batches = [[bytes(rng.choice(list(letters), size=int(n)).astype(np.uint8)) for n in rng.integers(300, 1500, size=T)]
                for _ in range(2)]
     whole = api.SignalGenerator(prof, fl, k, mean, stdv, seed=9, num_workers=T, mode=api.MODE_CERTIFIED)
     parts = [api.SignalGenerator(prof, fl, k, mean, stdv, seed=9, num_workers=T, mode=api.MODE_CERTIFIED,
                                  worker_lo=lo, worker_hi=hi) for lo, hi in ((0, 5), (5, 12))]
+    orac = orc.Oracle(prof, fl, k, mean, stdv, 9, num_workers=T)
     for reads in batches:
         bw = whole.submit(reads)
         sw = bw.signal()
+        for i, w in enumerate(orac.run_batch_seqs(reads, want_ss=False)):      # ... which is the oracle's -t 12 run
+            np.testing.assert_array_equal(sw[bw.sig_off[i]:bw.sig_off[i + 1]], w.sig, err_msg=f"one context, read {i}")
         for g, (lo, hi) in zip(parts, ((0, 5), (5, 12))):
             idx = [i for i in range(T) if lo <= i < hi]
             bp = g.submit([reads[i] for i in idx], workers=idx)
@@ -153,8 +154,22 @@ def test_worker_shards_equal_one_context():
     with pytest.raises(api.SqgError):
         parts[0].submit([batches[0][0]], workers=[7])          # a worker this context does not own
     whole.close()
+    orac.close()
     for g in parts:
         g.close()
+
+
+def test_worker_shards_equal_one_context():
+    """Multi-GPU sharding at the C ABI: two contexts owning workers [0,5) and [5,12) (as two GPUs would)
+    reproduce, read for read, what one context owning all 12 workers produces -- over two batches."""
+    _worker_shards_equal_one_context("dna-r10-prom", 9, b"ACGT")
+
+
+def test_worker_shards_equal_one_context_with_the_methylation_table():
+    """the same under SQG_METH, k = 6: a worker's seeds lie 5^k + 10 apart (src/sim.c:325), so a shard that placed its workers' streams
+    by 4^k would draw other numbers than the context that owns them all"""
+    from squigulator_amd import profiles
+    _worker_shards_equal_one_context("dna-r9-prom", 6, b"ACGTM", sflags=profiles.SQ_METH)
 
 
 def test_paf_sam_goldens_from_device_dwell():

@@ -3,6 +3,7 @@ and generates a contiguous range of each batch's reads; the per-stream sample co
 Here G ranks are G contexts on one GPU and the exchange goes through the host; the result must be the oracle's
 single-process run, read for read."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -43,20 +44,27 @@ def _ranges(n, G):
     return list(zip(cut[:-1], cut[1:]))
 
 
-def _run(name, fasta, T, G, batches, rlen, sflags=0, mode=api.SAMPLE_DNA, seed=42, arith=api.MODE_CERTIFIED):
+def _run(name, fasta, T, G, batches, rlen, sflags=0, mode=api.SAMPLE_DNA, seed=42, arith=api.MODE_CERTIFIED, meth_freq=None):
+    """meth_freq: a --meth-freq table -- the contexts get the 5-letter pore table (5^k rows: that many counts per worker are exchanged) and
+    the sampler methylates the CpGs of every read of the batch, skipped ones included"""
     hip = Hip()
     prof, fl = profiles.get_profile(name)
     k = profiles.default_kmer_size(fl)
-    mean, stdv = model.synthetic_model(k)
+    if meth_freq:
+        sflags |= profiles.SQ_METH
+    mean, stdv = model.synthetic_model(k, meth=bool(meth_freq))
     orac = orc.Oracle(prof, fl | sflags, k, mean, stdv, seed, num_workers=T, rlen=rlen)
-    ref = orac.load_ref(fasta, None)
+    ref = orac.load_ref(fasta, None, meth_freq)
     gens = []
     for _ in range(G):
         g = api.SignalGenerator(prof, fl | sflags, k, mean, stdv, seed, num_workers=T, mode=arith)
         g.load_genome(_contigs(ref), rlen, mode)
+        if meth_freq:
+            g.set_meth(_contigs(ref), [ref.names[i].decode() for i in range(ref.num_ref)], meth_freq)
         g.set_range_mode(True)
         gens.append(g)
-    n_rows = T * (1 << (2 * k))
+    n_rows = T * len(mean)                                   # 4^k streams per worker, 5^k with the methylation table
+    assert n_rows == T * (5 ** k if meth_freq else 1 << (2 * k))
     for nb in batches:
         want = orac.run_batch(nb)
         rng = _ranges(nb, G)
@@ -71,8 +79,10 @@ def _run(name, fasta, T, G, batches, rlen, sflags=0, mode=api.SAMPLE_DNA, seed=4
         for g, (b, (lo, hi)) in enumerate(zip(bs, rng)):
             sig, dw = b.signal(), b.dwell()
             s = b.sampled
+            seqs = b.reads() if meth_freq and hi > lo else None     # (the Ms a read carries: the sequence itself is compared too)
             for i in range(hi - lo):
                 w = want[lo + i]
+                assert seqs is None or seqs[i] == w.seq, f"rank {g} read {lo + i}: sequence differs"
                 assert (s["ref_idx"][i], s["ref_pos"][i], s["rlen"][i], chr(s["strand"][i])) == (w.ref_idx, w.ref_pos_st, w.rlen, w.strand)
                 np.testing.assert_array_equal(dw[b.ev_off[i]:b.ev_off[i + 1]], w.ss, err_msg=f"rank {g} read {lo + i}")
                 np.testing.assert_array_equal(sig[b.sig_off[i]:b.sig_off[i + 1]], w.sig, err_msg=f"rank {g} read {lo + i}")
@@ -107,22 +117,21 @@ def test_a_rank_with_an_empty_range_still_follows_the_streams():
     _run("dna-r9-prom", NCOV, 1, 3, [2, 2, 5], rlen=500)
 
 
-@pytest.mark.gpu
-def test_host_reads_with_skip_reads_match_the_oracle():
-    """reads staged from the host: the ranks call sqg_skip_reads for the reads before and after their range"""
+def _host_reads_with_skip_reads(name, k, letters, sflags=0):
     hip = Hip()
     rng_ = np.random.default_rng(3)
-    prof, fl = profiles.get_profile("dna-r9-prom")
-    mean, stdv = model.synthetic_model(6)
+    prof, fl = profiles.get_profile(name)
+    fl |= sflags
+    mean, stdv = model.synthetic_model(k, meth=bool(sflags & profiles.SQ_METH))
     T, G = 2, 2
-    batches = [[bytes(rng_.choice(list(b"ACGT"), int(m)).astype(np.uint8)) for m in rng_.integers(5, 900, nb)] for nb in (11, 6)]
-    orac = orc.Oracle(prof, fl, 6, mean, stdv, 5, num_workers=T)
+    batches = [[bytes(rng_.choice(list(letters), int(m)).astype(np.uint8)) for m in rng_.integers(5, 900, nb)] for nb in (11, 6)]
+    orac = orc.Oracle(prof, fl, k, mean, stdv, 5, num_workers=T)
     want = [orac.run_batch_seqs(bt) for bt in batches]
     orac.close()
-    gens = [api.SignalGenerator(prof, fl, 6, mean, stdv, 5, num_workers=T, mode=api.MODE_CERTIFIED) for _ in range(G)]
+    gens = [api.SignalGenerator(prof, fl, k, mean, stdv, 5, num_workers=T, mode=api.MODE_CERTIFIED) for _ in range(G)]
     for g in gens:
         g.set_range_mode(True)
-    n_rows = T * 4096
+    n_rows = T * len(mean)
     for bi, bt in enumerate(batches):
         n = len(bt)
         wk = np.array([gens[0].L.sqg_worker_of(i, n, T) for i in range(n)], np.int32)
@@ -139,14 +148,51 @@ def test_host_reads_with_skip_reads_match_the_oracle():
             pa = hip.to_device(sum(counts[g + 1:], np.zeros(n_rows, np.uint64)))
             b.run_end(pb, pa).wait()
             hip.free(pb); hip.free(pa)
-            sig = b.signal()
+            sig, dw = b.signal(), b.dwell()
             lo = rng[g][0]
             for i in range(b.n_reads):
                 np.testing.assert_array_equal(sig[b.sig_off[i]:b.sig_off[i + 1]], want[bi][lo + i].sig, err_msg=f"batch {bi} read {lo + i}")
-                assert b.offset[i] == want[bi][lo + i].offset
+                np.testing.assert_array_equal(dw[b.ev_off[i]:b.ev_off[i + 1]], want[bi][lo + i].ss, err_msg=f"batch {bi} read {lo + i} (dwell)")
+                assert b.offset[i] == want[bi][lo + i].offset and b.median_before[i] == want[bi][lo + i].median_before
             b.free()
     for g in gens:
         g.close()
+
+
+@pytest.mark.gpu
+def test_host_reads_with_skip_reads_match_the_oracle():
+    """reads staged from the host: the ranks call sqg_skip_reads for the reads before and after their range"""
+    _host_reads_with_skip_reads("dna-r9-prom", 6, b"ACGT")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,k", [("dna-r9-prom", 6), ("dna-r10-prom", 7)], ids=["k6", "k7"])
+def test_host_reads_holding_M_with_skip_reads_match_the_oracle(name, k):
+    """the same with the 5-letter table: the counts of 5^k streams per worker (4 and 20 partitions, the last one ragged) are exchanged,
+    and a skipped read moves its worker's streams by 5^k-wide rows; no preset has a 7-mer table: k is passed as it is"""
+    _host_reads_with_skip_reads(name, k, b"ACGTM" + b"ACGTM" + b"ACGTM" + b"mN", sflags=profiles.SQ_METH)
+
+
+# ---- the 5-letter methylation table: [T][5^k] counts per exchange, the sampler's rand_meth draws for reads outside the range
+MFREQ_DENSE = os.path.join(os.path.dirname(NCOV), "mfreq_dense.tsv")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,G,batches", [(1, 2, [9, 20, 4]), (2, 3, [12, 25])], ids=["t1_g2", "t2_g3"])
+def test_dna_r9_ranges_under_the_methylation_table(T, G, batches):
+    _run("dna-r9-prom", NCOV, T, G, batches, rlen=900, meth_freq=MFREQ_DENSE)
+
+
+@pytest.mark.gpu
+def test_nine_mer_methylation_counts_are_exchanged_as_sums():
+    """per-link rows of 5^9 streams: 7.8 MB per exchange vector"""
+    _run("dna-r10-prom", NCOV, 1, 2, [10, 14], rlen=700, meth_freq=MFREQ_DENSE)
+
+
+@pytest.mark.gpu
+def test_an_empty_range_still_spends_the_skipped_reads_methylation_draws():
+    """3 ranks, 2 reads per batch: one range is empty every time; sqg_batch_sample_range samples -- and methylates -- every read of the batch"""
+    _run("dna-r9-prom", NCOV, 1, 3, [2, 2, 5], rlen=500, meth_freq=MFREQ_DENSE)
 
 
 @pytest.mark.gpu

@@ -244,7 +244,10 @@ MFREQ_DENSE = os.path.join(INPUTS, "mfreq_dense.tsv")
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("T,batches,rlen,mf", [(1, [6, 5], 4000, MFREQ), (1, [40, 30], 1500, MFREQ_DENSE), (8, [8, 8, 8], 2500, MFREQ_DENSE),
-                                              (3, [20, 33], 1200, MFREQ_DENSE)], ids=["t1_ref_file", "t1_long_chain", "tk8", "t3"])
+                                              (3, [20, 33], 1200, MFREQ_DENSE),
+                                              # from 65536 events on the chains are cut: the reads carry their Ms from k_sampler.h into the links
+                                              (1, [60, 45], 1500, MFREQ_DENSE), (3, [70, 64], 1200, MFREQ_DENSE)],
+                         ids=["t1_ref_file", "t1_long_chain", "tk8", "t3", "t1_cut_chains", "t3_cut_chains"])
 def test_cpg_methylation_in_the_device_sampler(T, batches, rlen, mf):
     """--meth-freq: every CpG of a read's reference span draws from the worker's rand_meth stream in order; methylated Cs
     become 'M' (also on the '-' strand), the signal comes from the 5-letter table (src/genread.c:207-241, src/seq.h:45-74)"""

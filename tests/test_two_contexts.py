@@ -12,8 +12,8 @@ import orc
 from squigulator_amd import api, model, profiles, shard
 
 
-def _reads(rng, n, lo=300, hi=2500):
-    return [bytes(rng.choice(list(b"ACGT"), int(m)).astype(np.uint8)) for m in rng.integers(lo, hi, n)]
+def _reads(rng, n, lo=300, hi=2500, letters=b"ACGT"):
+    return [bytes(rng.choice(list(letters), int(m)).astype(np.uint8)) for m in rng.integers(lo, hi, n)]
 
 
 @pytest.mark.gpu
@@ -23,8 +23,9 @@ def test_contexts_on_threads_equal_one_context(name, T, G, K, extra_flags=0):
     prof, fl = profiles.get_profile(name)
     fl |= extra_flags
     k = profiles.default_kmer_size(fl)
-    mean, stdv = model.synthetic_model(k)
-    batches = [_reads(rng, K) for _ in range(3)]
+    meth = bool(fl & profiles.SQ_METH)                              # the 5-letter table: reads that hold M
+    mean, stdv = model.synthetic_model(k, meth=meth)
+    batches = [_reads(rng, K, letters=b"ACGTM" if meth else b"ACGT") for _ in range(3)]
     # the whole job in one context
     one = api.SignalGenerator(prof, fl, k, mean, stdv, 42, num_workers=T, mode=api.MODE_CERTIFIED)
     want = []
@@ -69,6 +70,13 @@ def test_contexts_on_threads_equal_one_context(name, T, G, K, extra_flags=0):
     for bi in range(len(batches)):
         for i in range(len(batches[bi])):
             np.testing.assert_array_equal(got[bi][i], want[bi][i], err_msg=f"batch {bi} read {i}")
+
+
+@pytest.mark.gpu
+def test_contexts_on_threads_equal_one_context_with_the_methylation_table():
+    """SQG_METH, k = 6, the smallest row above: a shard's worker seeds advance by 5^k + 10 per worker (src/sim.c:325); with 100 reads of
+    some 1400 events per worker the chains are cut and handed out over 4 partitions"""
+    test_contexts_on_threads_equal_one_context("dna-r9-prom", 4, 2, 400, extra_flags=profiles.SQ_METH)
 
 
 @pytest.mark.gpu
