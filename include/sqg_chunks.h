@@ -63,7 +63,7 @@ typedef struct {          /* all DEVICE memory of the context's device, owned by
 int sqg_chunk_plan(sqg_ctx_t *ctx, sqg_batch_t *b, const sqg_chunk_cfg_t *cfg, int64_t *chunk_off, int64_t *n_chunks);
 /* device: fills *out for a batch that has been run; returns when everything in *out is complete.  The batch must still own its
  * device results (sqg.h: until two more batches have been run), else SQG_ESEQUENCE.  Not for SQG_PREFIX contexts (SQG_EINVAL):
- * adaptor, poly-A and stall have no base labels.  Works on the context's stream and waits for it. */
+ * adaptor, poly-A and stall have no base labels; sqg_segments.h finds them and chunks the insert.  Works on the context's stream and waits for it. */
 int sqg_batch_chunks(sqg_ctx_t *ctx, sqg_batch_t *b, const sqg_chunk_cfg_t *cfg, const sqg_chunk_out_t *out);
 
 #ifdef __cplusplus

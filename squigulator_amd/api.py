@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h and include/sqg_targets.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h and include/sqg_segments.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -90,7 +90,7 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
-             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC")
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS")
 
 # include/sqg_chunks.h: bound by load_library only when the library has them (the CPU backend does not)
 EXPORTS_CHUNKS = ("sqg_chunk_plan", "sqg_batch_chunks")
@@ -112,6 +112,14 @@ EXPORTS_TARGETS = ["sqg_batch_chunk_targets"]
 
 class CChunkTargets(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("clean", "clean_raw", "moves", "kmer", "med2", "mad4")]
+
+
+# include/sqg_segments.h: bound the same way
+EXPORTS_SEGMENTS = ("sqg_batch_segments", "sqg_chunk_plan_trimmed", "sqg_batch_chunks_trimmed", "sqg_batch_chunk_targets_trimmed")
+
+
+class CSegments(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("seg", "shift")]
 
 
 class Chunks:
@@ -239,6 +247,15 @@ def load_library(path: str | None = None):
     if all(hasattr(L, n) for n in EXPORTS_TARGETS):
         L.sqg_batch_chunk_targets.restype = C.c_int
         L.sqg_batch_chunk_targets.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
+    if all(hasattr(L, n) for n in EXPORTS_SEGMENTS):
+        L.sqg_batch_segments.restype = C.c_int
+        L.sqg_batch_segments.argtypes = [vp, vp, C.POINTER(CSegments)]
+        L.sqg_chunk_plan_trimmed.restype = C.c_int
+        L.sqg_chunk_plan_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(i64), C.POINTER(i64)]
+        L.sqg_batch_chunks_trimmed.restype = C.c_int
+        L.sqg_batch_chunks_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
+        L.sqg_batch_chunk_targets_trimmed.restype = C.c_int
+        L.sqg_batch_chunk_targets_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
     _libs[path] = L
     return L
 
@@ -469,37 +486,61 @@ class Batch:
             raise SqgError(-1, "chunks", f"unknown dtype / norm {dtype!r} / {norm!r}")
         return CChunkCfg(int(chunk_len), int(chunk_len if stride is None else stride), int(max_label), dt & 0xffffffff, nm & 0xffffffff)
 
-    def chunk_plan(self, chunk_len: int, stride: int | None = None):
-        """(chunk_off [n_reads+1], n_chunks): the first chunk of every read, from the batch's sig_off (sqg_chunk_plan; host only)"""
+    def _trimmed(self, name, trim):
+        """the library call `name`, or with trim its counterpart of include/sqg_segments.h (which cuts the inserts and takes SQG_PREFIX contexts)"""
+        if not trim:
+            return name
+        if not hasattr(self.gen.L, "sqg_batch_segments"):
+            raise SqgError(-1, "segments", "this backend has no sqg_batch_segments (include/sqg_segments.h)")
+        return name + "_trimmed"
+
+    def segments(self):
+        """(seg [n_reads, 5], shift [n_reads, 2]): int64 tensors on the batch's device -- every read's stall / adaptor / poly-A / insert
+        bounds in stored samples and the range of the RNA adaptor's level shift (sqg_batch_segments, include/sqg_segments.h)"""
+        import torch
+        self._trimmed("", True)
+        dev = torch.device("cuda", self.gen.device)
+        seg = torch.zeros((self.n_reads, 5), dtype=torch.int64, device=dev)
+        shift = torch.zeros((self.n_reads, 2), dtype=torch.int64, device=dev)
+        out = CSegments(*(t.data_ptr() if t.numel() else None for t in (seg, shift)))
+        torch.cuda.synchronize(dev)
+        self.gen._chk(self.gen.L.sqg_batch_segments(self.gen.ctx, self.handle, C.byref(out)), "sqg_batch_segments")
+        return seg, shift
+
+    def chunk_plan(self, chunk_len: int, stride: int | None = None, trim: bool = False):
+        """(chunk_off [n_reads+1], n_chunks): the first chunk of every read, from the batch's sig_off (sqg_chunk_plan; host only).
+        trim=True: of every read's insert (sqg_chunk_plan_trimmed, include/sqg_segments.h; device work)"""
         cfg = self._chunk_cfg(chunk_len, stride, 0, CHUNK_F16, CHUNK_MEDMAD)
         off = np.zeros(self.n_reads + 1, np.int64)
         nc = C.c_int64()
-        self.gen._chk(self.gen.L.sqg_chunk_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nc)),
-                      "sqg_chunk_plan")
+        name = self._trimmed("sqg_chunk_plan", trim)
+        self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nc)), name)
         return off, int(nc.value)
 
-    def _chunk_job(self, chunk_len, stride, max_label, dtype, norm):
+    def _chunk_job(self, chunk_len, stride, max_label, dtype, norm, trim=False):
         """what chunks() and chunk_targets() share: (cfg, chunk_off, n_chunks, device, new, call) -- new(shape, dtype): an output tensor;
         call(name, out, *tensors): the C struct `out` filled with the tensors' addresses, then the library's `name` on this batch"""
         import torch
         cfg = self._chunk_cfg(chunk_len, stride, max_label, dtype, norm)
-        off, nc = self.chunk_plan(chunk_len, cfg.stride)
+        off, nc = self.chunk_plan(chunk_len, cfg.stride, trim)
         dev = torch.device("cuda", self.gen.device)
         new = lambda shape, dt: (torch.zeros if nc == 0 else torch.empty)(shape, dtype=dt, device=dev)   # noqa: E731
         def call(name, out, *tensors):
             out = out(*(t.data_ptr() if t is not None and t.numel() else None for t in tensors))
             torch.cuda.synchronize(dev)                     # (the allocator's pending work on these blocks, if any, before another stream writes them)
+            name = self._trimmed(name, trim)
             self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), name)
         return cfg, off, nc, dev, new, call
 
     def chunks(self, chunk_len: int, stride: int | None = None, max_label: int = 0, dtype="f16", norm="medmad",
-               signal: bool = True, labels: bool = True) -> Chunks:
+               signal: bool = True, labels: bool = True, trim: bool = False) -> Chunks:
         """Fixed-length, per-read normalised windows of the batch's signal and their base labels, made on the device
         (sqg_batch_chunks): torch tensors signal [n_chunks, L] (float16 / float32), labels [n_chunks, W] (uint8, 0 = padding),
         label_len, chunk_read, chunk_start [n_chunks], med2, mad4 [n_reads].  signal=False / labels=False leave those passes out
-        (the tensors are then None)."""
+        (the tensors are then None).  trim=True: chunks of every read's insert, the way into SQG_PREFIX contexts
+        (sqg_batch_chunks_trimmed, include/sqg_segments.h)."""
         import torch
-        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, max_label, dtype, norm)
+        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, max_label, dtype, norm, trim)
         ch = Chunks(n_chunks=nc, chunk_off=off,
                     signal=new((nc, cfg.chunk_len), torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16) if signal else None,
                     labels=new((nc, cfg.max_label), torch.uint8) if labels else None,
@@ -511,16 +552,18 @@ class Batch:
         return ch
 
     def chunk_targets(self, chunk_len: int, stride: int | None = None, dtype="f16", norm="medmad", clean: bool = True,
-                      clean_raw: bool = False, moves: bool = True, kmer: bool = False, chunks: Chunks | None = None) -> Chunks:
+                      clean_raw: bool = False, moves: bool = True, kmer: bool = False, chunks: Chunks | None = None,
+                      trim: bool = False) -> Chunks:
         """Per-sample targets for the chunks Batch.chunks() cuts with the same chunk_len / stride (sqg_batch_chunk_targets,
         include/sqg_targets.h): torch tensors [n_chunks, L] on the batch's device -- clean (float16 / float32: the noise-free signal on
         the noisy read's scale), clean_raw (int16: what --ideal-amp writes), moves (uint8: 1 where an event starts), kmer (uint32 bit
         patterns in an int32 tensor: the pore-table row).  Those not asked for are None.  chunks=: a Chunks of this batch, whose med2 /
-        mad4 are passed in instead of being computed again."""
+        mad4 are passed in instead of being computed again.  trim=True: for the chunks of chunks(..., trim=True)
+        (sqg_batch_chunk_targets_trimmed, include/sqg_segments.h)."""
         import torch
         if not hasattr(self.gen.L, "sqg_batch_chunk_targets"):
             raise SqgError(-1, "chunk_targets", "this backend has no sqg_batch_chunk_targets (include/sqg_targets.h)")
-        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, 0, dtype, norm)
+        cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, 0, dtype, norm, trim)
         row = lambda want, dt: new((nc, cfg.chunk_len), dt) if want else None           # noqa: E731
         tg = Chunks(n_chunks=nc, chunk_off=off, clean=row(clean, torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16),
                     clean_raw=row(clean_raw, torch.int16), moves=row(moves, torch.uint8), kmer=row(kmer, torch.int32))

@@ -85,7 +85,10 @@ struct ChunkScratch {
     unsigned int* d_wide = nullptr; size_t wide_cap = 0;       // the list of reads whose codes span more than the LDS histogram
     unsigned int* d_ghist = nullptr; size_t ghist_cap = 0;     // the global histograms of the generic statistics paths
     uint32_t* d_start = nullptr; size_t start_cap = 0;         // [n_events] first sample of every event within its read (k_target_scan)
-    void release() { for (void* p : {(void*)d_off, (void*)d_const, (void*)d_read, (void*)d_ev, (void*)d_wide, (void*)d_ghist, (void*)d_start}) (void)hipFree(p);
+    long long* d_span = nullptr; size_t span_cap = 0; std::vector<long long> h_span;   // [2][n_reads] the inserts' spans of the slab, lo then hi (k_segments)
+    ChunkView* d_view = nullptr; size_t view_cap = 0;          // [n_reads] their events and bases
+    const void* span_of = nullptr; unsigned long long span_run = 0;   // the batch (and its run index) spans and views were last made for
+    void release() { for (void* p : {(void*)d_off, (void*)d_const, (void*)d_read, (void*)d_ev, (void*)d_wide, (void*)d_ghist, (void*)d_start, (void*)d_span, (void*)d_view}) (void)hipFree(p);
                      *this = ChunkScratch(); }
 };
 

@@ -2,11 +2,11 @@
 // Host side of include/sqg_targets.h; included by sqg_hip.hip behind h_chunks.h, whose checks, plan and statistics pass it uses.
 #pragma once
 
-extern "C" int sqg_batch_chunk_targets(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_t* cfg, const sqg_chunk_targets_t* tg) {
-    static const char who[] = "sqg_batch_chunk_targets";
+// sqg_batch_chunk_targets, and sqg_batch_chunk_targets_trimmed (h_segments.h) with trimmed
+static int targets_run(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, const sqg_chunk_targets_t* tg, const char* who, bool trimmed) {
     sqg_chunk_cfg_t cf{};
     if (cfg) { cf = *cfg; cf.max_label = 0; }                            // (ignored here)
-    int rc = chunk_check(c, b, cfg ? &cf : nullptr, who);
+    int rc = chunk_check(c, b, cfg ? &cf : nullptr, who, trimmed);
     if (rc) return rc;
     auto bad = [&](const char* what) { c->err = std::string(who) + ": " + what; return SQG_EINVAL; };
     if (!tg) return bad("tg must not be NULL");
@@ -16,12 +16,12 @@ extern "C" int sqg_batch_chunk_targets(sqg_ctx_t* c, sqg_batch_t* b, const sqg_c
     // (stricter than every output set needs -- only the statistics read the signal slab, a constant-dwell context reads no dwells -- but
     // one rule for the call, the one sqg_batch_chunks has: the batch owns its device results and its dwell set, or nothing is written)
     ChunkJob J;
-    if ((rc = chunk_begin(c, b, &cf, who, c->use_dwell_stream, &J))) return rc;
+    if ((rc = chunk_begin(c, b, &cf, who, c->use_dwell_stream, &J, trimmed))) return rc;
     const int n = b->n;
     const long long n_chunks = J.n_chunks;
     if (n_chunks == 0 || !(tg->clean || tg->clean_raw || tg->moves || tg->kmer)) return SQG_OK;      // (n == 0 too) before the device is touched
     for (int i = 0; i < n; i++)
-        if (J.plan[i + 1] > J.plan[i] && b->sig_off[(size_t)i + 1] - b->sig_off[(size_t)i] > (long long)UINT32_MAX) {
+        if (J.plan[i + 1] > J.plan[i] && J.hi[i] - J.lo[i] > (long long)UINT32_MAX) {
             c->err = std::string(who) + ": a read exceeds UINT32_MAX samples";
             return SQG_EOVERFLOW;
         }
@@ -31,7 +31,7 @@ extern "C" int sqg_batch_chunk_targets(sqg_ctx_t* c, sqg_batch_t* b, const sqg_c
     const hipStream_t st = J.st;
     const ReadDesc* reads = (const ReadDesc*)b->d_reads;
     const bool want_consts = tg->clean && cf.norm == SQG_CHUNK_MEDMAD;
-    if (want_consts && !tg->med2) { if ((rc = chunk_stats_run(c, b, P))) return rc; }
+    if (want_consts && !tg->med2) { if ((rc = chunk_stats_run(c, b, J))) return rc; }
     else if (want_consts) hipLaunchKernelGGL(k_chunk_consts, dim3((unsigned)((n + CHUNK_WG - 1) / CHUNK_WG)), dim3(CHUNK_WG), 0, st, P, (const int*)tg->med2, (const int*)tg->mad4);
     hipLaunchKernelGGL(k_chunk_index, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
     // pass A: the event starts
@@ -54,8 +54,15 @@ extern "C" int sqg_batch_chunk_targets(sqg_ctx_t* c, sqg_batch_t* b, const sqg_c
 #undef TGT_CLEAN
 #undef TGT_CASE
     }
+    // the RNA adaptor's level-shift window, where it reaches into an insert (include/sqg_segments.h)
+    if (trimmed && T.rna && (c->cfg.flags & SQG_PREFIX) && (tg->clean || tg->clean_raw))
+        hipLaunchKernelGGL(k_target_shift, dim3((unsigned)std::min<long long>(n_chunks, 4096)), dim3(64), 0, st, P, T, clean, segments_shift_code(c));
     HIPCHK(c, hipGetLastError());
     if ((rc = dbg_sync(c, "k_target_emit"))) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return SQG_OK;
+}
+
+extern "C" int sqg_batch_chunk_targets(sqg_ctx_t* c, sqg_batch_t* b, const sqg_chunk_cfg_t* cfg, const sqg_chunk_targets_t* tg) {
+    return targets_run(c, b, cfg, tg, "sqg_batch_chunk_targets", false);
 }

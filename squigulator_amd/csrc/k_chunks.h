@@ -19,9 +19,21 @@
 #define CHUNK_WIDE_SLOTS 32          // workgroups (and global histogram pairs) of k_chunk_stats_wide
 #define CHUNK_BIG (1LL << 60)
 
+// What the chunk kernels take for "the read" when it is not the whole stored read (include/sqg_segments.h: the insert of a read with an
+// attached prefix; written per read by k_segments, k_segments.h).  Events and bases count from the read's first; samples in generation order
+// from the span's first.  32 bytes.
+struct ChunkView {
+    long long sh_lo, sh_hi;          // the part of the RNA adaptor's level-shift window inside the span, generation order relative to the span (empty: lo >= hi)
+    int ev0, nev;                    // the span's events [ev0, ev0 + nev) of chain 0
+    int base0;                       // first base of event ev0
+    int pad;                         // (to the struct's 8-byte alignment: written, so that the scratch holds no stale bytes)
+};
+
 struct ChunkParams {
     const int16_t* sig;              // the batch's signal slab
-    const long long* sig_off;        // [n_reads+1]
+    const long long* lo;             // [n_reads] every read's span of the slab, [lo, hi): the batch's sig_off and sig_off + 1, or the
+    const long long* hi;             //           spans k_segments wrote
+    const ChunkView* view;           // [n_reads] the spans' events and bases; null: the whole read (ReadDesc's ev_off, base_off, ne0)
     const long long* chunk_off;      // [n_reads+1] first chunk of every read
     int n_reads;
     long long n_chunks;
@@ -102,7 +114,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats(ChunkParams P) {
     __shared__ unsigned long long sh[8];
     __shared__ int res[2], mm[2 * (CHUNK_WG / 64)];
     const int r = blockIdx.x, t = threadIdx.x;
-    const long long o = P.sig_off[r], n = P.sig_off[r + 1] - o;
+    const long long o = P.lo[r], n = P.hi[r] - o;
     if (n <= 0) { if (t == 0) chunk_write_stats(P, r, 0, 0); return; }
     if (n > P.one_wg_max) return;                           // the long path's
     const int16_t* p = P.sig + o;
@@ -161,7 +173,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats_wide(ChunkParams P) {
     const unsigned int count = P.wide_list[0];
     for (unsigned int at = blockIdx.x; at < count; at += gridDim.x) {
         const int r = (int)P.wide_list[1 + at];
-        const long long o = P.sig_off[r], n = P.sig_off[r + 1] - o;
+        const long long o = P.lo[r], n = P.hi[r] - o;
         for (int i = threadIdx.x; i < 2 * CHUNK_GBINS; i += CHUNK_WG) __hip_atomic_store(&H[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();
         __syncthreads();
@@ -177,7 +189,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats_wide(ChunkParams P) {
 
 // the long path, read r: H (zeroed by the host) <- the histogram, the workgroups sharing the samples
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_hist_long(ChunkParams P, int r) {
-    const long long o = P.sig_off[r], n = P.sig_off[r + 1] - o;
+    const long long o = P.lo[r], n = P.hi[r] - o;
     unsigned int* H = P.ghist;
     chunk_for_samples(P.sig + o, n, blockIdx.x, gridDim.x, [&](int v) { atomicAdd(&H[v + 32768], 1u); });
 }
@@ -185,7 +197,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_select_long(ChunkParams P, i
     __shared__ unsigned long long sh[8];
     __shared__ int res[2];
     int med2, mad4;
-    chunk_select_global(P.ghist, P.ghist + CHUNK_GBINS, P.sig_off[r + 1] - P.sig_off[r], sh, res, &med2, &mad4);
+    chunk_select_global(P.ghist, P.ghist + CHUNK_GBINS, P.hi[r] - P.lo[r], sh, res, &med2, &mad4);
     if (threadIdx.x == 0) chunk_write_stats(P, r, med2, mad4);
 }
 
@@ -243,7 +255,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, const Re
     for (long long c = (long long)blockIdx.x * cpb + sub; c < P.n_chunks; c += (long long)gridDim.x * cpb) {
         const int r = P.chunk_read[c];
         const long long j = c - P.chunk_off[r];
-        const int16_t* src0 = P.sig + P.sig_off[r] + j * P.S;
+        const int16_t* src0 = P.sig + P.lo[r] + j * P.S;
         const float2 cs = P.consts[r];
         double offset = 0.0;
         if (PA) offset = reads[r].offset;
@@ -295,18 +307,26 @@ __device__ static inline void chunk_mark(const ChunkGeom& G, int2* ev, long long
 
 __device__ static inline uint32_t chunk_label_code(uint8_t b, int meth) { return (meth && b == 'M') ? 5u : base_code(b) + 1u; }
 
+// the events and bases the chunks of read r are cut from: the whole of chain 0, or the view's part of it
+struct ChunkOrigin { long long ev_off, base_off; int ne; };
+__device__ static inline ChunkOrigin chunk_origin(const ChunkParams& P, const ReadDesc& rd, int r) {
+    if (!P.view) return {rd.ev_off, rd.base_off, rd.ne0};
+    const ChunkView v = P.view[r];
+    return {rd.ev_off + v.ev0, rd.base_off + v.base0, v.nev};
+}
+
 // E[e], the first sample of event e relative to its read, is the exclusive prefix sum of the read's dwells.  f(e, E[e], dwell[e]) for every
-// event of read rd, the whole workgroup calling: 4 consecutive events per thread, tiles of 4 * CHUNK_WG events, the sum carried from tile
+// event of the origin og (e and E count from its first event), the whole workgroup calling: 4 consecutive events per thread, tiles of 4 * CHUNK_WG events, the sum carried from tile
 // to tile.  dwell == nullptr: a constant-dwell context, every dwell is const_sps.  sh: the 8 words of chunk_scan_excl.
 template <class F>
-__device__ static inline void chunk_for_event_starts(const ReadDesc& rd, const uint16_t* dwell, int const_sps, unsigned long long* sh, F f) {
-    const int ne = rd.ne0, t = threadIdx.x;
+__device__ static inline void chunk_for_event_starts(const ChunkOrigin& og, const uint16_t* dwell, int const_sps, unsigned long long* sh, F f) {
+    const int ne = og.ne, t = threadIdx.x;
     unsigned long long carry = 0;
     for (int base = 0; base < ne; base += 4 * CHUNK_WG) {
         const int e0 = base + 4 * t;
         int d[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (dwell ? (int)dwell[rd.ev_off + e0 + q] : const_sps) : 0;
+        for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (dwell ? (int)dwell[og.ev_off + e0 + q] : const_sps) : 0;
         unsigned long long total;
         unsigned long long E = carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total);
         carry += total;
@@ -328,11 +348,11 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const 
     ChunkGeom G;
     G.c0 = P.chunk_off[r]; G.nc = P.chunk_off[r + 1] - G.c0;
     if (G.nc <= 0) return;
-    G.n = P.sig_off[r + 1] - P.sig_off[r]; G.L = P.L; G.S = P.S; G.rna = rna;
+    G.n = P.hi[r] - P.lo[r]; G.L = P.L; G.S = P.S; G.rna = rna;
     G.small = !div64 && G.n < (1LL << 31);                  // div64: the development build's test hook, the 64-bit divisions on every read
-    const ReadDesc rd = reads[r];
-    const int ne = rd.ne0;
-    chunk_for_event_starts(rd, dwell, const_sps, sh, [&, ne](int e, long long E, int d) {
+    const ChunkOrigin og = chunk_origin(P, reads[r], r);
+    const int ne = og.ne;
+    chunk_for_event_starts(og, dwell, const_sps, sh, [&, ne](int e, long long E, int d) {
         if (e == 0) chunk_mark(G, ev, -CHUNK_BIG, 0, 0);
         chunk_mark(G, ev, E, e == ne - 1 ? CHUNK_BIG : E + d, e + 1);
     });
@@ -353,7 +373,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const 
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int i = x + q;
-                const uint32_t code = i < len ? chunk_label_code(bases[rd.base_off + (rna ? e1 - 1 - i : e0 + i)], meth) : 0u;
+                const uint32_t code = i < len ? chunk_label_code(bases[og.base_off + (rna ? e1 - 1 - i : e0 + i)], meth) : 0u;
                 v |= code << (8 * q);
             }
             if (pack4) *reinterpret_cast<uint32_t*>(row + x) = v;

@@ -35,10 +35,10 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_scan(ChunkParams P, const R
     __shared__ unsigned long long sh[8];
     const int r = blockIdx.x;
     if (P.chunk_off[r + 1] == P.chunk_off[r]) return;       // no chunk asks for this read's events
-    const ReadDesc rd = reads[r];
+    const ChunkOrigin og = chunk_origin(P, reads[r], r);
     __builtin_assume(dwell != nullptr);                     // (the host launches this pass in dwell-stream contexts only)
-    chunk_for_event_starts(rd, dwell, 0, sh, [&](int e, unsigned long long E, int) {
-        ev_start[rd.ev_off + e] = (uint32_t)E;              // (the host has checked: the read has at most UINT32_MAX samples)
+    chunk_for_event_starts(og, dwell, 0, sh, [&](int e, unsigned long long E, int) {
+        ev_start[og.ev_off + e] = (uint32_t)E;              // (the host has checked: the read has at most UINT32_MAX samples)
     });
 }
 
@@ -96,11 +96,12 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
             c = n_tiles == 1 ? item : item / n_tiles;
             tl = (int)(item - c * n_tiles);
             r = P.chunk_read[c];
-            const long long j = c - P.chunk_off[r], n = P.sig_off[r + 1] - P.sig_off[r];
+            const long long j = c - P.chunk_off[r], n = P.hi[r] - P.lo[r];
             gt0 = (T.rna ? n - j * P.S - P.L : j * P.S) + (long long)tl * TGT_TILE;        // the tile's first generation-order sample
             tlen = min(TGT_TILE, P.L - tl * TGT_TILE);
             const ReadDesc rd = T.reads[r];
-            ne = rd.ne0; ev_off = rd.ev_off; base_off = rd.base_off; offset = rd.offset;
+            const ChunkOrigin og = chunk_origin(P, rd, r);
+            ne = og.ne; ev_off = og.ev_off; base_off = og.base_off; offset = rd.offset;
             if (T.ev_start) { E = T.ev_start + ev_off; e_lo = tgt_lower_bound(E, ne, (uint32_t)gt0); }
             else e_lo = (int)min((gt0 + T.const_sps - 1) / T.const_sps, (long long)ne);
         }

@@ -1,4 +1,4 @@
-// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h and include/sqg_targets.h.
+// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h and include/sqg_segments.h.
 //
 // One translation unit: the gfx950 kernels (sqg_kernels.h: k_common.h, k_events.h, k_samples.h, k_sampler.h,
 // k_svb.h) and the host side of the C ABI (h_*.h: context/batch management, staging, launches, results).
@@ -29,6 +29,7 @@
 #include "../../include/sqg.h"
 #include "../../include/sqg_chunks.h"
 #include "../../include/sqg_targets.h"
+#include "../../include/sqg_segments.h"
 
 #include "sqg_kernels.h"
 
@@ -42,3 +43,4 @@
 #include "h_blow5.h"      // sqg_blow5_*: the native BLOW5 writer
 #include "h_chunks.h"     // sqg_chunk_plan, sqg_batch_chunks (include/sqg_chunks.h)
 #include "h_targets.h"    // sqg_batch_chunk_targets (include/sqg_targets.h)
+#include "h_segments.h"   // sqg_batch_segments, sqg_chunk_plan_trimmed, sqg_batch_chunks_trimmed, sqg_batch_chunk_targets_trimmed (include/sqg_segments.h)
