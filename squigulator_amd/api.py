@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h and include/sqg_segments.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h and include/sqg_sites.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -120,6 +120,20 @@ EXPORTS_SEGMENTS = ("sqg_batch_segments", "sqg_chunk_plan_trimmed", "sqg_batch_c
 
 class CSegments(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("seg", "shift")]
+
+
+# include/sqg_sites.h: bound the same way
+EXPORTS_SITES = ("sqg_site_plan", "sqg_batch_sites")
+SITE_OUTPUTS = ("signal", "label", "site_read", "site_pos", "win_start", "context", "ctx_start", "med2", "mad4")
+
+
+class CSiteCfg(C.Structure):
+    _fields_ = [("win_len", C.c_int32), ("before", C.c_int32), ("focus", C.c_int32), ("ctx_len", C.c_int32), ("ctx_before", C.c_int32),
+                ("dtype", C.c_uint32), ("norm", C.c_uint32)]
+
+
+class CSiteOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SITE_OUTPUTS]
 
 
 class Chunks:
@@ -256,6 +270,11 @@ def load_library(path: str | None = None):
         L.sqg_batch_chunks_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
         L.sqg_batch_chunk_targets_trimmed.restype = C.c_int
         L.sqg_batch_chunk_targets_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
+    if all(hasattr(L, n) for n in EXPORTS_SITES):
+        L.sqg_site_plan.restype = C.c_int
+        L.sqg_site_plan.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(i64), C.POINTER(i64)]
+        L.sqg_batch_sites.restype = C.c_int
+        L.sqg_batch_sites.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(CSiteOut)]
     _libs[path] = L
     return L
 
@@ -577,6 +596,54 @@ class Batch:
                     raise SqgError(-1, "chunk_targets", f"chunks= must carry this batch's med2 / mad4: int32 [{self.n_reads}] on {dev}")
         call("sqg_batch_chunk_targets", CChunkTargets, tg.clean, tg.clean_raw, tg.moves, tg.kmer, *st)
         return tg
+
+    def _site_cfg(self, win_len, before, focus, ctx_len, ctx_before, dtype, norm):
+        if not hasattr(self.gen.L, "sqg_batch_sites"):
+            raise SqgError(-1, "sites", "this backend has no sqg_batch_sites (include/sqg_sites.h)")
+        dt = {"f16": CHUNK_F16, "f32": CHUNK_F32}.get(dtype, dtype)
+        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
+        if not isinstance(dt, int) or not isinstance(nm, int):
+            raise SqgError(-1, "sites", f"unknown dtype / norm {dtype!r} / {norm!r}")
+        L, B = int(win_len), int(ctx_len)
+        return CSiteCfg(L, int(L // 2 if before is None else before), int(self.gen.kmer_size // 2 if focus is None else focus), B,
+                        int(B // 2 if ctx_before is None else ctx_before), dt & 0xffffffff, nm & 0xffffffff)
+
+    def site_plan(self, win_len: int, before: int | None = None, focus: int | None = None):
+        """(site_off [n_reads+1], n_sites): the first CpG site of every read for windows of win_len samples, `before` of them in front of
+        the anchor event (default win_len / 2), the site's base at position `focus` of that event's k-mer (default k / 2)
+        (sqg_site_plan, include/sqg_sites.h; device work and a copy-back of the per-read counts)"""
+        return self._site_plan(self._site_cfg(win_len, before, focus, 0, 0, CHUNK_F16, CHUNK_MEDMAD))
+
+    def _site_plan(self, cfg):
+        off = np.zeros(self.n_reads + 1, np.int64)
+        ns = C.c_int64()
+        self.gen._chk(self.gen.L.sqg_site_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ns)), "sqg_site_plan")
+        return off, int(ns.value)
+
+    def sites(self, win_len: int, before: int | None = None, focus: int | None = None, ctx_len: int = 0, ctx_before: int | None = None,
+              dtype="f16", norm="medmad", outputs=None) -> Chunks:
+        """One normalised window of signal around every CpG site of the batch with the site's methylation label, made on the device
+        (sqg_batch_sites, include/sqg_sites.h): torch tensors signal [n_sites, L] (float16 / float32), label (uint8: 1 where the read
+        carries 'M'), site_read, site_pos (int32), win_start (int64) [n_sites], context [n_sites, B] (uint8 label codes around the
+        site), ctx_start [n_sites, B + 1] (int32: where each context base's samples start in the window), med2, mad4 [n_reads].
+        before / focus / ctx_before default to win_len / 2, k / 2, ctx_len / 2.  outputs: the names wanted (default all); the others are None."""
+        import torch
+        cfg = self._site_cfg(win_len, before, focus, ctx_len, ctx_before, dtype, norm)
+        want = set(SITE_OUTPUTS if outputs is None else outputs)
+        if want - set(SITE_OUTPUTS):
+            raise SqgError(-1, "sites", f"unknown outputs {sorted(want - set(SITE_OUTPUTS))}")
+        off, ns = self._site_plan(cfg)                      # (validates all of cfg: the shapes below are sane)
+        dev = torch.device("cuda", self.gen.device)
+        L, B = cfg.win_len, cfg.ctx_len
+        shapes = dict(signal=((ns, L), torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16), label=((ns,), torch.uint8),
+                      site_read=((ns,), torch.int32), site_pos=((ns,), torch.int32), win_start=((ns,), torch.int64),
+                      context=((ns, B), torch.uint8), ctx_start=((ns, B + 1), torch.int32),
+                      med2=((self.n_reads,), torch.int32), mad4=((self.n_reads,), torch.int32))
+        st = Chunks(n_sites=ns, site_off=off, **{n: (torch.zeros(sh, dtype=dt, device=dev) if n in want else None) for n, (sh, dt) in shapes.items()})
+        out = CSiteOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(st, n) for n in SITE_OUTPUTS)))
+        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
+        self.gen._chk(self.gen.L.sqg_batch_sites(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_sites")
+        return st
 
     def free(self):
         if self.handle:

@@ -92,6 +92,17 @@ struct ChunkScratch {
                      *this = ChunkScratch(); }
 };
 
+// device scratch of sqg_site_plan and sqg_batch_sites (h_sites.h), grown by ensure(): the plan and the per-site records
+struct SiteScratch {
+    int* d_count = nullptr; size_t count_cap = 0; std::vector<int> h_count;        // [n_reads] sites of every read (k_site_scan<0>)
+    long long* d_off = nullptr; size_t off_cap = 0; std::vector<long long> h_off;   // [n_reads+1] first site of every read, device and host
+    SiteRec* d_rec = nullptr; size_t rec_cap = 0;              // [n_sites] (k_site_scan<1> -> k_site_emit)
+    uint8_t* d_skip = nullptr; size_t skip_cap = 0;            // [n_reads] the batch's reads shorter than a k-mer
+    const void* plan_of = nullptr; unsigned long long plan_run = 0; int plan_key[3] = {0, 0, 0};   // the batch (and its run index) and the win_len / before / focus the plan was last made for
+    void release() { for (void* p : {(void*)d_count, (void*)d_off, (void*)d_rec, (void*)d_skip}) (void)hipFree(p);
+                     *this = SiteScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -227,6 +238,7 @@ struct sqg_ctx {
     int cal_runs_left = 12;
     void* b5_reader = nullptr; int b5_reader_buf = -1; void (*b5_reader_drain)(void* writer, bool unbind) = nullptr;
     ChunkScratch chunk;                                        // sqg_batch_chunks, sqg_batch_chunk_targets (h_chunks.h, h_targets.h)
+    SiteScratch site;                                          // sqg_site_plan, sqg_batch_sites (h_sites.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

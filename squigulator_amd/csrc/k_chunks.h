@@ -318,8 +318,10 @@ __device__ static inline ChunkOrigin chunk_origin(const ChunkParams& P, const Re
 // E[e], the first sample of event e relative to its read, is the exclusive prefix sum of the read's dwells.  f(e, E[e], dwell[e]) for every
 // event of the origin og (e and E count from its first event), the whole workgroup calling: 4 consecutive events per thread, tiles of 4 * CHUNK_WG events, the sum carried from tile
 // to tile.  dwell == nullptr: a constant-dwell context, every dwell is const_sps.  sh: the 8 words of chunk_scan_excl.
-template <class F>
-__device__ static inline void chunk_for_event_starts(const ChunkOrigin& og, const uint16_t* dwell, int const_sps, unsigned long long* sh, F f) {
+// The tile form, for a caller with workgroup-wide work of its own per tile (k_sites.h ranks its sites there): g(e0, E[e0], d) once per
+// thread and tile, every thread calling -- its 4 events e0 .. e0 + 3 and their dwells, 0 for those behind the origin's last.
+template <class G>
+__device__ static inline void chunk_for_event_tiles(const ChunkOrigin& og, const uint16_t* dwell, int const_sps, unsigned long long* sh, G g) {
     const int ne = og.ne, t = threadIdx.x;
     unsigned long long carry = 0;
     for (int base = 0; base < ne; base += 4 * CHUNK_WG) {
@@ -328,14 +330,21 @@ __device__ static inline void chunk_for_event_starts(const ChunkOrigin& og, cons
 #pragma unroll
         for (int q = 0; q < 4; q++) d[q] = e0 + q < ne ? (dwell ? (int)dwell[og.ev_off + e0 + q] : const_sps) : 0;
         unsigned long long total;
-        unsigned long long E = carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total);
+        const unsigned long long E = carry + chunk_scan_excl((unsigned long long)(d[0] + d[1] + d[2] + d[3]), sh, &total);
         carry += total;
+        g(e0, E, d);
+    }
+}
+template <class F>
+__device__ static inline void chunk_for_event_starts(const ChunkOrigin& og, const uint16_t* dwell, int const_sps, unsigned long long* sh, F f) {
+    const int ne = og.ne;
+    chunk_for_event_tiles(og, dwell, const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (e0 + q < ne) f(e0 + q, E, d[q]);
             E += (unsigned long long)d[q];
         }
-    }
+    });
 }
 
 // The chunk boundaries in (E[e], E[e] + dwell[e]] belong to event e + 1 (the first event that starts at or behind them), those at or before 0

@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h and k_segments.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h and k_sites.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -17,6 +17,7 @@
 //   k_chunk_*     per-read median / MAD (or the constants from statistics passed in), normalised fixed-length chunks and their base labels (include/sqg_chunks.h)
 //   k_segments    the segments of a read with an attached prefix (stall, adaptor, poly-A, insert) from the dwell sums at its edges, and the insert's
 //                 view for the chunk kernels; k_target_shift: the adaptor's level shift where it reaches an insert (include/sqg_segments.h)
+//   k_site_*      the CpG sites of every read from the dwell scan, then a normalised window, the bases around it and their places in the window per site (include/sqg_sites.h)
 //   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
@@ -42,3 +43,4 @@
 #include "k_chunks.h"
 #include "k_targets.h"
 #include "k_segments.h"
+#include "k_sites.h"
