@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h and include/sqg_sites.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h and include/sqg_events.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -134,6 +134,19 @@ class CSiteCfg(C.Structure):
 
 class CSiteOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SITE_OUTPUTS]
+
+
+# include/sqg_events.h: bound the same way
+EXPORTS_EVENTS = ("sqg_batch_events",)
+EVENT_OUTPUTS = ("ev_read", "ev_start", "ev_len", "sum", "sumsq", "vmin", "vmax", "kmer", "level_raw", "seg", "mean", "sd", "med2", "mad4")
+
+
+class CEventCfg(C.Structure):
+    _fields_ = [("norm", C.c_uint32), ("trim", C.c_int32)]
+
+
+class CEventOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in EVENT_OUTPUTS]
 
 
 class Chunks:
@@ -275,6 +288,9 @@ def load_library(path: str | None = None):
         L.sqg_site_plan.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(i64), C.POINTER(i64)]
         L.sqg_batch_sites.restype = C.c_int
         L.sqg_batch_sites.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(CSiteOut)]
+    if all(hasattr(L, n) for n in EXPORTS_EVENTS):
+        L.sqg_batch_events.restype = C.c_int
+        L.sqg_batch_events.argtypes = [vp, vp, C.POINTER(CEventCfg), C.POINTER(CEventOut)]
     _libs[path] = L
     return L
 
@@ -644,6 +660,38 @@ class Batch:
         torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
         self.gen._chk(self.gen.L.sqg_batch_sites(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_sites")
         return st
+
+    def events(self, norm="pa", trim: bool = False, outputs=None) -> Chunks:
+        """The per-event signal table of the batch, made on the device (sqg_batch_events, include/sqg_events.h): one row per event in
+        the order of dwell(), read r's rows being [ev_off[r], ev_off[r+1]).  torch tensors [n_events]: ev_read (int32), ev_start (int64:
+        first stored sample within the read), ev_len (int32), sum, sumsq (int64), vmin, vmax (int16), kmer (uint32 bit patterns in an
+        int32 tensor: the pore-table row), level_raw (int16), seg (uint8: 0 stall, 1 adaptor, 2 poly-A, 3 insert), mean, sd (float32,
+        normalised by norm: "pa" or "medmad"); med2, mad4 [n_reads] (int32), over the whole read or with trim over its insert.
+        outputs: the names wanted (default all); the others are None."""
+        import torch
+        if not hasattr(self.gen.L, "sqg_batch_events"):
+            raise SqgError(-1, "events", "this backend has no sqg_batch_events (include/sqg_events.h)")
+        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
+        if not isinstance(nm, int):
+            raise SqgError(-1, "events", f"unknown norm {norm!r}")
+        want = set(EVENT_OUTPUTS if outputs is None else outputs)
+        if want - set(EVENT_OUTPUTS):
+            raise SqgError(-1, "events", f"unknown outputs {sorted(want - set(EVENT_OUTPUTS))}")
+        cfg = CEventCfg(nm & 0xffffffff, int(trim))
+        if self.res is None and self.handle:
+            r = CResult()                                   # (the row count; a batch that has not been run: the library's SQG_ESEQUENCE below)
+            ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
+        else:
+            ne = int(self.n_events)
+        dev = torch.device("cuda", self.gen.device)
+        dts = dict(ev_read=torch.int32, ev_start=torch.int64, ev_len=torch.int32, sum=torch.int64, sumsq=torch.int64, vmin=torch.int16, vmax=torch.int16,
+                   kmer=torch.int32, level_raw=torch.int16, seg=torch.uint8, mean=torch.float32, sd=torch.float32, med2=torch.int32, mad4=torch.int32)
+        ev = Chunks(n_events=ne, **{n: (torch.zeros(self.n_reads if n in ("med2", "mad4") else ne, dtype=dts[n], device=dev) if n in want else None)
+                                    for n in EVENT_OUTPUTS})
+        out = CEventOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(ev, n) for n in EVENT_OUTPUTS)))
+        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
+        self.gen._chk(self.gen.L.sqg_batch_events(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_events")
+        return ev
 
     def free(self):
         if self.handle:

@@ -103,6 +103,14 @@ struct SiteScratch {
                      *this = SiteScratch(); }
 };
 
+// device scratch of sqg_batch_events (h_events_table.h), grown by ensure(): what the reduce pass needs of columns the caller did not ask for
+struct EventScratch {
+    long long* d_start = nullptr; size_t start_cap = 0;        // [n_events] first stored sample of every event within its read (k_evtab_scan)
+    int* d_read = nullptr; size_t read_cap = 0;                // [n_events] event -> read
+    void release() { for (void* p : {(void*)d_start, (void*)d_read}) (void)hipFree(p);
+                     *this = EventScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -239,6 +247,7 @@ struct sqg_ctx {
     void* b5_reader = nullptr; int b5_reader_buf = -1; void (*b5_reader_drain)(void* writer, bool unbind) = nullptr;
     ChunkScratch chunk;                                        // sqg_batch_chunks, sqg_batch_chunk_targets (h_chunks.h, h_targets.h)
     SiteScratch site;                                          // sqg_site_plan, sqg_batch_sites (h_sites.h)
+    EventScratch event;                                        // sqg_batch_events (h_events_table.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -56,6 +56,7 @@ extern "C" void sqg_destroy(sqg_ctx_t* ctx) {
     (void)hipFree(ctx->d_b5meta); (void)hipFree(ctx->d_b5out); (void)hipFree(ctx->d_b5tab); (void)hipFree(ctx->d_b5size); for (auto* q : ctx->h_b5out) if (q) (void)hipHostFree(q); if (ctx->h_b5meta) (void)hipHostFree(ctx->h_b5meta);
     ctx->chunk.release();
     ctx->site.release();
+    ctx->event.release();
     (void)hipFree(ctx->d_genome); (void)hipFree(ctx->d_contig_off); (void)hipFree(ctx->d_cum); (void)hipFree(ctx->d_nprefix);
     (void)hipFree(ctx->d_trans_csum); (void)hipFree(ctx->d_trans_idx); (void)hipFree(ctx->d_samp);
     (void)hipFree(ctx->d_meth); (void)hipFree(ctx->d_meth_has); (void)hipFree(ctx->d_meth_st);

@@ -1,0 +1,151 @@
+// k_events_table.h -- the per-event signal table of a batch (include/sqg_events.h): one row per event, its place, k-mer and level, then the sums of its samples
+// Part of the device code of the per-read signal path; included through sqg_kernels.h (see there for the overview).  (k_events.h is the generator's event pass.)
+//
+//   k_evtab_scan         one workgroup per read over the dwell scan of k_chunks.h (chunk_for_event_tiles) with an origin that spans both chains:
+//                        ev_start from the E the scan carries, and the columns that need no sample -- ev_read, ev_len, seg (k_segments.h's event
+//                        ranges), kmer (k_targets.h's rank, on the event's own chain) and level_raw (src/gensig.c:270).  ev_start and ev_read go
+//                        to scratch when the caller does not want them: the reduce pass finds an event's samples through them.
+//   k_evtab_reduce<PA>   a flat grid over the batch's events, one event per lane: a read of 100 events and one of 100 000 load the device alike,
+//                        and no workgroup walks a read's events one behind the other (the label pass's latency chain: profiles/chunks.md).  An event
+//                        of at most EVT_LANE_MAX samples is reduced by its lane; a longer one -- a dwell goes up to 65 535 -- by the whole
+//                        wavefront, one after the other in lane order: the bounds of those loops come from a ballot and a broadcast, the same for
+//                        every lane.  An event starts at any sample of the slab, so the loads are the aligned 4-byte words that cover it, their
+//                        halves taken or left (k_chunk_emit's scheme; no misaligned wide load is issued, no word without a sample of the event is
+//                        touched).  mean / sd are derived in the same pass, in FP64 as the header states them.
+// The statistics are k_chunks.h's pass (h_events_table.h runs chunk_stats_run over the whole reads or their inserts).
+#pragma once
+
+#define EVT_LANE_MAX 64                              // samples up to which a lane reduces an event alone (33 word loads at the most)
+
+struct EventParams {
+    const ReadDesc* reads;
+    const uint8_t* bases;
+    const float2* model;                             // {level_mean, -}
+    const uint16_t* dwell;                           // the batch's dwells; null: a constant-dwell context, every dwell is const_sps
+    const long long* sig_off;                        // [n_reads+1]
+    const int16_t* sig;                              // the batch's signal slab
+    const float2* consts;                            // [n_reads] {median, 1 / (1.4826 MAD)} (k_chunk_stats); MEDMAD rows only
+    int const_sps, k, meth, rna, n_reads, kind;      // rna: the signal is stored reversed; kind: SEG_NONE / SEG_DNA / SEG_RNA (k_segments.h)
+    int p0, p1;                                      // SEG_DNA: events of the stall, of stall + adaptor.  SEG_RNA: bases of the poly-A, of poly-A + adaptor
+    long long n_events;
+    double range, dig;
+    long long* ev_start; int* ev_read;               // the caller's or scratch: never null when the reduce pass runs
+    int* ev_len; uint32_t* kmer; int16_t* level_raw; uint8_t* seg;                          // the caller's, may be null
+    long long* sum; long long* sumsq; int16_t* vmin; int16_t* vmax; float* mean; float* sd;   // the caller's, may be null
+};
+
+__global__ __launch_bounds__(CHUNK_WG) void k_evtab_scan(EventParams Q) {
+    __shared__ unsigned long long sh[8];
+    const int r = blockIdx.x;
+    const ReadDesc rd = Q.reads[r];
+    const long long n = Q.sig_off[r + 1] - Q.sig_off[r];
+    const int ne0 = rd.ne0, ne = rd.ne0 + max(rd.ne1, 0);
+    // the event ranges of include/sqg_segments.h: DNA [0, a) stall, [a, b) adaptor, then insert; RNA [0, a) insert, [a, b) poly-A, [b, ne0) adaptor, chain 1 stall
+    int a = 0, b = 0;
+    if (Q.kind == SEG_DNA) { a = min(Q.p0, ne0); b = min(Q.p1, ne0); }
+    else if (Q.kind == SEG_RNA) { const int len = max(rd.len0 - Q.p1, 0); a = min(len, ne0); b = min(len + Q.p0, ne0); }
+    const uint8_t* bp0 = Q.bases + rd.base_off;
+    const uint8_t* bp1 = bp0 + rd.len0 - ne0;               // chain 1's event e has its k-mer at bp0 + len0 + (e - ne0)
+    chunk_for_event_tiles(ChunkOrigin{rd.ev_off, rd.base_off, ne}, Q.dwell, Q.const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int e = e0 + q;
+            if (e < ne) {
+                const long long at = rd.ev_off + e;
+                if (Q.ev_start) Q.ev_start[at] = Q.rna ? n - (long long)E - d[q] : (long long)E;
+                if (Q.ev_read) Q.ev_read[at] = r;
+                if (Q.ev_len) Q.ev_len[at] = d[q];
+                if (Q.seg) Q.seg[at] = (uint8_t)(Q.kind == SEG_DNA ? (e < a ? 0 : e < b ? 1 : 3) : Q.kind == SEG_RNA ? (e < a ? 3 : e < b ? 2 : e < ne0 ? 1 : 0) : 3);
+                if (Q.kmer || Q.level_raw) {
+                    const uint32_t rank = kmer_rank_wide((e < ne0 ? bp0 : bp1) + e, Q.k, Q.meth);
+                    if (Q.kmer) Q.kmer[at] = rank;
+                    if (Q.level_raw) Q.level_raw[at] = to_i16((double)Q.model[rank].x * Q.dig / Q.range - rd.offset);      // src/gensig.c:270
+                }
+            }
+            E += (unsigned long long)d[q];
+        }
+    });
+}
+
+struct EventAcc {
+    long long sum; unsigned long long sq; int mn, mx;
+    __device__ void take(uint32_t half) {
+        const int v = (int)(int16_t)(half & 0xffffu);
+        sum += v; sq += (unsigned long long)(v * v); mn = min(mn, v); mx = max(mx, v);      // (v * v <= 2^30)
+    }
+};
+
+template <bool PA>
+__global__ __launch_bounds__(CHUNK_WG) void k_evtab_reduce(EventParams Q) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.sig);              // the slab in aligned words: sample s is half s & 1 of word s >> 1
+    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
+        const long long i = base + threadIdx.x;
+        const bool have = i < Q.n_events;
+        int r = 0, len = 0;
+        long long s0 = 0;                                                        // the event's first sample in the slab
+        if (have) {
+            r = Q.ev_read[i];
+            len = Q.dwell ? (int)Q.dwell[i] : Q.const_sps;
+            s0 = Q.sig_off[r] + Q.ev_start[i];
+        }
+        EventAcc A{0, 0, 32767, -32768};
+        if (have && len <= EVT_LANE_MAX) {
+            long long s = s0;
+            const long long end = s0 + len;
+            if ((s & 1) && s < end) { A.take(W[s >> 1] >> 16); s++; }
+            for (; s + 2 <= end; s += 2) { const uint32_t w = W[s >> 1]; A.take(w); A.take(w >> 16); }
+            if (s < end) A.take(W[s >> 1]);
+        }
+        // the long events of this wavefront, one at a time by all of its lanes: `todo`, `ls0` and `lend` are the same in every lane
+        unsigned long long todo = __ballot(have && len > EVT_LANE_MAX);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const long long ls0 = __shfl(s0, src, 64);
+            const long long lend = ls0 + (long long)__shfl(len, src, 64);
+            const long long w_lo = ls0 >> 1, w_hi = (lend - 1) >> 1;            // the words that hold a sample of the event
+            EventAcc B{0, 0, 32767, -32768};
+            for (long long wb = w_lo; wb <= w_hi; wb += 64) {
+                const long long w = wb + lane;
+                if (w <= w_hi) {
+                    const uint32_t x = W[w];
+                    if (2 * w >= ls0) B.take(x);                                // (2 w < lend: w <= w_hi)
+                    if (2 * w + 1 < lend) B.take(x >> 16);                      // (2 w + 1 >= ls0: w >= w_lo)
+                }
+            }
+#pragma unroll
+            for (int d = 32; d; d >>= 1) {
+                B.sum += __shfl_xor(B.sum, d, 64); B.sq += __shfl_xor(B.sq, d, 64);
+                B.mn = min(B.mn, __shfl_xor(B.mn, d, 64)); B.mx = max(B.mx, __shfl_xor(B.mx, d, 64));
+            }
+            if (lane == src) A = B;
+        }
+        if (!have) continue;
+        if (Q.sum) Q.sum[i] = A.sum;
+        if (Q.sumsq) Q.sumsq[i] = (long long)A.sq;
+        if (Q.vmin) Q.vmin[i] = (int16_t)A.mn;
+        if (Q.vmax) Q.vmax[i] = (int16_t)A.mx;
+        if (Q.mean || Q.sd) {
+            // include/sqg_events.h: one rounding per operation (the build has -ffp-contract=off); double sqrt is correctly rounded on this
+            // device, as the exact sample path relies on (k_common.h: box_muller_exact)
+            const double dl = (double)len, ds = (double)A.sum;
+            const double m = ds / dl;
+            double v = ((double)A.sq - ds * m) / dl;
+            v = v < 0 ? 0 : v;
+            const double s = sqrt(v);
+            float mean, sd;
+            if (PA) {
+                const double offset = Q.reads[r].offset;
+                mean = (float)(((m + offset) * Q.range) / Q.dig);
+                sd = (float)((s * Q.range) / Q.dig);
+            } else {
+                const float2 cs = Q.consts[r];                                   // cs.x = med2 / 2 exactly: |med2| < 2^17
+                mean = (float)((m - (double)cs.x) * (double)cs.y);
+                sd = (float)(s * (double)cs.y);
+            }
+            if (Q.mean) Q.mean[i] = mean;
+            if (Q.sd) Q.sd[i] = sd;
+        }
+    }
+}

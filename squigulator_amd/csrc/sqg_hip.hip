@@ -1,4 +1,4 @@
-// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h and include/sqg_sites.h.
+// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h and include/sqg_events.h.
 //
 // One translation unit: the gfx950 kernels (sqg_kernels.h: k_common.h, k_events.h, k_samples.h, k_sampler.h,
 // k_svb.h) and the host side of the C ABI (h_*.h: context/batch management, staging, launches, results).
@@ -31,6 +31,7 @@
 #include "../../include/sqg_targets.h"
 #include "../../include/sqg_segments.h"
 #include "../../include/sqg_sites.h"
+#include "../../include/sqg_events.h"
 
 #include "sqg_kernels.h"
 
@@ -46,3 +47,4 @@
 #include "h_targets.h"    // sqg_batch_chunk_targets (include/sqg_targets.h)
 #include "h_segments.h"   // sqg_batch_segments, sqg_chunk_plan_trimmed, sqg_batch_chunks_trimmed, sqg_batch_chunk_targets_trimmed (include/sqg_segments.h)
 #include "h_sites.h"      // sqg_site_plan, sqg_batch_sites (include/sqg_sites.h)
+#include "h_events_table.h"   // sqg_batch_events (include/sqg_events.h)
