@@ -98,7 +98,9 @@ typedef struct {
     float amp_noise;            /* core->opt.amp_noise                                       */
     uint32_t kmer_size;         /* core->kmer_size, 1..9                                     */
     const sqg_kmer_t *model;    /* core->model, 4^k rows (host memory, copied)               */
-    int64_t seed;               /* core->opt.seed (must be != 0 as in the reference CLI)     */
+    int64_t seed;               /* core->opt.seed, taken as it is: |seed| + T*(num_kmer+10) <= 9.0e10, else SQG_EINVAL.  0 is a seed like
+                                 * any other here -- it is the reference's CLI that replaces 0 by the time of day before it seeds
+                                 * (src/sim.c:1026); stream seeds are reduced mod 2^31-1 ("LCG")              */
     int32_t num_workers;        /* T = core->opt.num_thread: virtual workers in the job      */
     int32_t worker_lo;          /* this context owns workers [worker_lo, worker_hi):         */
     int32_t worker_hi;          /*   0,T on one GPU; a shard of them per GPU otherwise       */

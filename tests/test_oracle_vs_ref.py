@@ -14,7 +14,7 @@ import pytest
 
 import orc
 import simrun
-from refvec_cases import LIVE_CMD, LIVE_SEEDS, REFVEC_CASES
+from refvec_cases import LIVE_CMD, LIVE_SEEDS, REFVEC_CASES, SEED_CASES
 from squigulator_amd import model, options
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,8 +39,9 @@ def _check(reads, v):
         so += rlen; go += nsig; eo += nss
 
 
-@pytest.mark.parametrize("cid,cmd", REFVEC_CASES, ids=[c[0] for c in REFVEC_CASES])
+@pytest.mark.parametrize("cid,cmd", REFVEC_CASES + SEED_CASES, ids=[c[0] for c in REFVEC_CASES + SEED_CASES])
 def test_oracle_matches_committed_reference_vectors(cid, cmd):
+    """(the seed_* cases: seeds outside [1, 2^31 - 1), where the oracle's uncorrected int64 state is itself on trial)"""
     v = np.load(os.path.join(VEC, cid + ".npz"))
     assert str(v["cmd"]) == cmd, "fixture was generated from a different command line; rerun tools/make_refvec.py"
     o, k, names, lengths, reads, orac = simrun.run_oracle(cmd)

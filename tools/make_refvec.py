@@ -8,6 +8,7 @@ SYNTHETIC pore model (squigulator_amd.model.synthetic_model), so the oracle -- a
 the HIP path -- can be checked on machines without the reference.  Fixtures are data only.
 
 usage: python tools/make_refvec.py            (rebuilds the harness first)
+       python tools/make_refvec.py seed_      (only the cases whose id starts with one of the given prefixes)
 """
 import os
 import struct
@@ -102,10 +103,13 @@ def pack(reads):
 
 
 def main():
+    from refvec_cases import SEED_CASES       # (here, not at the top: tests import run_harness / pack from this module and need no case list)
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"])
     os.makedirs(OUT, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
-        for cid, cmd in REFVEC_CASES + [(f"live_seed{s}", LIVE_CMD.format(seed=s)) for s in LIVE_SEEDS]:
+        for cid, cmd in REFVEC_CASES + SEED_CASES + [(f"live_seed{s}", LIVE_CMD.format(seed=s)) for s in LIVE_SEEDS]:
+            if sys.argv[1:] and not cid.startswith(tuple(sys.argv[1:])):
+                continue
             reads, k = run_harness(cmd, tmp)
             np.savez_compressed(os.path.join(OUT, cid + ".npz"), cmd=np.array(cmd), k=np.array(k), **pack(reads))
             print(f"{cid}: {len(reads)} reads, {sum(len(r['sig']) for r in reads)} samples")
