@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h and include/sqg_events.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h and include/sqg_pileup.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -149,6 +149,39 @@ class CEventOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in EVENT_OUTPUTS]
 
 
+# include/sqg_pileup.h: bound the same way
+EXPORTS_PILEUP = ("sqg_batch_pileup",)
+PILEUP_OUTPUTS = ("n", "dwell", "dwell_sq", "mean_sum", "mean_sq", "sd_sum")
+PILEUP_BY_REF, PILEUP_BY_KMER = 0, 1
+PILEUP_SPLIT_STRAND, PILEUP_SPLIT_METH = 1, 2
+
+
+class CPileupCfg(C.Structure):
+    _fields_ = [("by", C.c_uint32), ("split", C.c_uint32), ("norm", C.c_uint32), ("trim", C.c_int32), ("segs", C.c_uint32),
+                ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+class COrigin(C.Structure):
+    _fields_ = [("key0", C.POINTER(C.c_int64)), ("step", C.POINTER(C.c_int8))]
+
+
+class CPileupOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PILEUP_OUTPUTS]
+
+
+class CPileupStat(C.Structure):
+    _fields_ = [("counted", C.c_int64), ("outside", C.c_int64)]
+
+
+class Pileup:
+    """What SignalGenerator.new_pileup() returns: the cfg of a pileup and its sums, torch tensors [planes, hi - lo] on the context's device
+    that Batch.pileup() adds to (include/sqg_pileup.h says what they hold); those not asked for are None"""
+
+    def __init__(self, cfg, planes, **kw):
+        self.cfg, self.planes = cfg, planes
+        self.__dict__.update(kw)
+
+
 class Chunks:
     """What Batch.chunks() returns: torch tensors on the context's device (include/sqg_chunks.h says what they hold)"""
 
@@ -291,6 +324,9 @@ def load_library(path: str | None = None):
     if all(hasattr(L, n) for n in EXPORTS_EVENTS):
         L.sqg_batch_events.restype = C.c_int
         L.sqg_batch_events.argtypes = [vp, vp, C.POINTER(CEventCfg), C.POINTER(CEventOut)]
+    if all(hasattr(L, n) for n in EXPORTS_PILEUP):
+        L.sqg_batch_pileup.restype = C.c_int
+        L.sqg_batch_pileup.argtypes = [vp, vp, C.POINTER(CPileupCfg), C.POINTER(COrigin), C.POINTER(CPileupOut), C.POINTER(CPileupStat)]
     _libs[path] = L
     return L
 
@@ -693,6 +729,26 @@ class Batch:
         self.gen._chk(self.gen.L.sqg_batch_events(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_events")
         return ev
 
+    def pileup(self, p: Pileup, origin=None):
+        """Adds the batch's events to the pileup `p` of SignalGenerator.new_pileup() (sqg_batch_pileup, include/sqg_pileup.h) and returns
+        (counted, outside).  origin=(key0, step): numpy arrays [n_reads] (int64, int8) in place of the sampler's origin -- for staged
+        batches, or another coordinate system"""
+        import torch
+        if not hasattr(self.gen.L, "sqg_batch_pileup"):
+            raise SqgError(-1, "pileup", "this backend has no sqg_batch_pileup (include/sqg_pileup.h)")
+        org = None
+        if origin is not None:
+            key0, step = np.ascontiguousarray(origin[0], np.int64), np.ascontiguousarray(origin[1], np.int8)
+            if key0.shape != (self.n_reads,) or step.shape != (self.n_reads,):
+                raise SqgError(-1, "pileup", f"origin=(key0, step) must be two arrays of {self.n_reads} elements")
+            org = COrigin(key0.ctypes.data_as(C.POINTER(C.c_int64)), step.ctypes.data_as(C.POINTER(C.c_int8)))
+        out = CPileupOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(p, n) for n in PILEUP_OUTPUTS)))
+        st = CPileupStat()
+        torch.cuda.synchronize(torch.device("cuda", self.gen.device))     # (the zero fills or the caller's own work on the sums, before another stream adds to them)
+        self.gen._chk(self.gen.L.sqg_batch_pileup(self.gen.ctx, self.handle, C.byref(p.cfg), C.byref(org) if org is not None else None,
+                                                  C.byref(out), C.byref(st)), "sqg_batch_pileup")
+        return int(st.counted), int(st.outside)
+
     def free(self):
         if self.handle:
             self.gen.L.sqg_batch_free(self.gen.ctx, self.handle)
@@ -780,6 +836,7 @@ class SignalGenerator:
             g.trans_csum = csum.ctypes.data_as(C.POINTER(C.c_float))
             g.trans_idx = idx.ctypes.data_as(C.POINTER(C.c_int32))
         self._chk(self.L.sqg_genome_load(self.ctx, C.byref(g)), "sqg_genome_load")
+        self.genome_len = int(off[-1])
 
     def set_meth(self, contigs, names, meth_freq_path: str):
         """--meth-freq FILE (tab separated: contig, 0-based position of a C, frequency) for the genome loaded with
@@ -794,6 +851,7 @@ class SignalGenerator:
         off[1:] = np.cumsum(np.asarray(contig_lens, np.int64))
         g = CGenome(len(contig_lens), C.c_void_p(d_seqs), off.ctypes.data_as(C.POINTER(C.c_int64)), rlen, mode, 0, None, None)
         self._chk(self.L.sqg_genome_load_device(self.ctx, C.byref(g)), "sqg_genome_load_device")
+        self.genome_len = int(off[-1])
 
     def set_range_mode(self, on: bool = True):
         """range sharding (include/sqg.h): this context owns all workers and generates a range of each batch's reads"""
@@ -827,6 +885,49 @@ class SignalGenerator:
                          strand=bytes(info.strand[:n]) if n else b"",
                          seq_off=np.ctypeslib.as_array(info.seq_off, shape=(n + 1,)).copy())
         return b
+
+    def new_pileup(self, by="ref", split=(), norm="pa", trim: bool = False, segs=None, lo: int | None = None, hi: int | None = None,
+                   outputs=None) -> Pileup:
+        """A zeroed pileup for Batch.pileup() (include/sqg_pileup.h): torch tensors [planes, hi - lo] on the context's device -- n (uint32
+        bit patterns in an int32 tensor), dwell, dwell_sq, mean_sum, mean_sq, sd_sum (int64; mean and sd in units of 1 / 4096).
+        by: "ref" (key: the forward-strand coordinate of the event's k-mer in the loaded genome) or "kmer" (its pore-table row);
+        split: any of "strand", "meth": a plane each; segs (by="kmer"): the segments counted, e.g. (3,) (default: the insert);
+        [lo, hi): the key window, default the whole loaded genome / all rows.  outputs: the names wanted (default all); the others are None."""
+        import torch
+        if not hasattr(self.L, "sqg_batch_pileup"):
+            raise SqgError(-1, "pileup", "this backend has no sqg_batch_pileup (include/sqg_pileup.h)")
+        bv = {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}.get(by, by)
+        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
+        if not isinstance(bv, int) or not isinstance(nm, int):
+            raise SqgError(-1, "pileup", f"unknown by / norm {by!r} / {norm!r}")
+        sp = 0
+        for name in ((split,) if isinstance(split, (str, int)) else split):
+            bit = {"strand": PILEUP_SPLIT_STRAND, "meth": PILEUP_SPLIT_METH}.get(name, name)
+            if not isinstance(bit, int):
+                raise SqgError(-1, "pileup", f"unknown split {name!r}")
+            sp |= bit
+        sg = 0
+        for q in (() if segs is None else segs):
+            sg |= 1 << int(q)
+        want = set(PILEUP_OUTPUTS if outputs is None else outputs)
+        if want - set(PILEUP_OUTPUTS):
+            raise SqgError(-1, "pileup", f"unknown outputs {sorted(want - set(PILEUP_OUTPUTS))}")
+        if lo is None:
+            lo = 0
+        if hi is None:
+            if bv == PILEUP_BY_KMER:
+                hi = 5 ** self.kmer_size if (self.flags & P.SQ_METH) else 1 << (2 * self.kmer_size)
+            else:
+                if getattr(self, "genome_len", None) is None:
+                    raise SqgError(-1, "pileup", "by=\"ref\" without hi= needs a loaded genome")
+                hi = self.genome_len
+        if hi < lo:
+            raise SqgError(-1, "pileup", "hi must not be below lo")
+        planes = (2 if sp & PILEUP_SPLIT_STRAND else 1) * (2 if sp & PILEUP_SPLIT_METH else 1)
+        cfg = CPileupCfg(bv & 0xffffffff, sp & 0xffffffff, nm & 0xffffffff, int(trim), sg & 0xffffffff, int(lo), int(hi))
+        dev = torch.device("cuda", self.device)
+        return Pileup(cfg, planes, **{n: (torch.zeros((planes, hi - lo), dtype=torch.int32 if n == "n" else torch.int64, device=dev) if n in want else None)
+                                      for n in PILEUP_OUTPUTS})
 
     def pinned(self, nbytes: int, dtype=np.uint8) -> np.ndarray:
         """A page-locked host array (sqg_host_alloc) for fast sqg_fetch_* destinations; freed with the generator."""

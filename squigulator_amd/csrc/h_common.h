@@ -111,6 +111,16 @@ struct EventScratch {
                      *this = EventScratch(); }
 };
 
+// device scratch of sqg_batch_pileup (h_pileup.h), grown by ensure(): the scan pass's columns the key or a split needs, the reads' origins, the counters
+struct PileupScratch {
+    uint32_t* d_kmer = nullptr; size_t kmer_cap = 0;           // [n_events] pore-table row of every event (k_evtab_scan)
+    uint8_t* d_seg = nullptr; size_t seg_cap = 0;              // [n_events] its segment
+    PileRead* d_pr = nullptr; size_t pr_cap = 0; std::vector<PileRead> h_pr;   // [n_reads] origin and insert of every read, device and host
+    unsigned long long* d_stat = nullptr; size_t stat_cap = 0;   // {counted, outside}
+    void release() { for (void* p : {(void*)d_kmer, (void*)d_seg, (void*)d_pr, (void*)d_stat}) (void)hipFree(p);
+                     *this = PileupScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -248,6 +258,7 @@ struct sqg_ctx {
     ChunkScratch chunk;                                        // sqg_batch_chunks, sqg_batch_chunk_targets (h_chunks.h, h_targets.h)
     SiteScratch site;                                          // sqg_site_plan, sqg_batch_sites (h_sites.h)
     EventScratch event;                                        // sqg_batch_events (h_events_table.h)
+    PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -2,6 +2,21 @@
 // Host side of include/sqg_events.h; included by sqg_hip.hip behind h_sites.h.  The lifetime rule, the job and the statistics pass are h_chunks.h's.
 #pragma once
 
+// what the kernels of k_events_table.h take of a run batch, all but the columns: sqg_batch_events and sqg_batch_pileup (h_pileup.h)
+static EventParams evtab_params(const sqg_ctx* c, const sqg_batch* b, const float2* consts) {
+    const bool prefix = (c->cfg.flags & SQG_PREFIX) != 0, rna = (c->cfg.flags & SQG_RNA) != 0;
+    EventParams Q{};
+    Q.reads = (const ReadDesc*)b->d_reads; Q.bases = (const uint8_t*)b->d_bases; Q.model = c->d_model;
+    Q.dwell = c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr;
+    Q.sig_off = c->slot[b->slot].d_sigoff; Q.sig = c->slot[b->slot].d_sig; Q.consts = consts;
+    Q.const_sps = (int)c->cfg.profile.dwell_mean; Q.k = c->k; Q.meth = (c->cfg.flags & SQG_METH) ? 1 : 0; Q.rna = rna ? 1 : 0; Q.n_reads = b->n;
+    Q.kind = !prefix ? SEG_NONE : rna ? SEG_RNA : SEG_DNA;
+    if (Q.kind == SEG_DNA) { Q.p0 = (int)strlen(kStallDna); Q.p1 = Q.p0 + (int)strlen(kAdaptorDna); }
+    if (Q.kind == SEG_RNA) { Q.p0 = kPolyA; Q.p1 = kPolyA + (int)strlen(kAdaptorRna); }
+    Q.n_events = b->n_events; Q.range = c->cfg.profile.range; Q.dig = c->cfg.profile.digitisation;
+    return Q;
+}
+
 extern "C" int sqg_batch_events(sqg_ctx_t* c, sqg_batch_t* b, const sqg_event_cfg_t* cfg, const sqg_event_out_t* out) {
     static const char who[] = "sqg_batch_events";
     if (!c) return SQG_EINVAL;
@@ -35,16 +50,7 @@ extern "C" int sqg_batch_events(sqg_ctx_t* c, sqg_batch_t* b, const sqg_event_cf
         const size_t ne = (size_t)b->n_events;
         if (want_reduce && !out->ev_start && (rc = ensure(c, (void**)&X.d_start, &X.start_cap, ne, sizeof(long long)))) return rc;
         if (want_reduce && !out->ev_read && (rc = ensure(c, (void**)&X.d_read, &X.read_cap, ne, sizeof(int)))) return rc;
-        const bool prefix = (c->cfg.flags & SQG_PREFIX) != 0, rna = (c->cfg.flags & SQG_RNA) != 0;
-        EventParams Q{};
-        Q.reads = (const ReadDesc*)b->d_reads; Q.bases = (const uint8_t*)b->d_bases; Q.model = c->d_model;
-        Q.dwell = c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr;
-        Q.sig_off = c->slot[b->slot].d_sigoff; Q.sig = c->slot[b->slot].d_sig; Q.consts = want_stats ? J.P.consts : (const float2*)nullptr;
-        Q.const_sps = (int)c->cfg.profile.dwell_mean; Q.k = c->k; Q.meth = (c->cfg.flags & SQG_METH) ? 1 : 0; Q.rna = rna ? 1 : 0; Q.n_reads = n;
-        Q.kind = !prefix ? SEG_NONE : rna ? SEG_RNA : SEG_DNA;
-        if (Q.kind == SEG_DNA) { Q.p0 = (int)strlen(kStallDna); Q.p1 = Q.p0 + (int)strlen(kAdaptorDna); }
-        if (Q.kind == SEG_RNA) { Q.p0 = kPolyA; Q.p1 = kPolyA + (int)strlen(kAdaptorRna); }
-        Q.n_events = b->n_events; Q.range = c->cfg.profile.range; Q.dig = c->cfg.profile.digitisation;
+        EventParams Q = evtab_params(c, b, want_stats ? J.P.consts : (const float2*)nullptr);
         Q.ev_start = out->ev_start ? (long long*)out->ev_start : want_reduce ? X.d_start : (long long*)nullptr;
         Q.ev_read = out->ev_read ? out->ev_read : want_reduce ? X.d_read : (int*)nullptr;
         Q.ev_len = out->ev_len; Q.kmer = out->kmer; Q.level_raw = out->level_raw; Q.seg = out->seg;

@@ -75,6 +75,64 @@ struct EventAcc {
     }
 };
 
+// The samples of the events of one wavefront, one event per lane: `take` says whether this lane's event [s0, s0 + len) of the slab is wanted
+// (the same code for every lane of the wavefront: the long events are reduced by all of them).  k_evtab_reduce and k_pileup (k_pileup.h).
+__device__ __forceinline__ EventAcc evtab_take(const uint32_t* W, const bool take, const int len, const long long s0, const int lane) {
+    EventAcc A{0, 0, 32767, -32768};
+    if (take && len <= EVT_LANE_MAX) {
+        long long s = s0;
+        const long long end = s0 + len;
+        if ((s & 1) && s < end) { A.take(W[s >> 1] >> 16); s++; }
+        for (; s + 2 <= end; s += 2) { const uint32_t w = W[s >> 1]; A.take(w); A.take(w >> 16); }
+        if (s < end) A.take(W[s >> 1]);
+    }
+    // the long events of this wavefront, one at a time by all of its lanes: `todo`, `ls0` and `lend` are the same in every lane
+    unsigned long long todo = __ballot(take && len > EVT_LANE_MAX);
+    while (todo) {
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const long long ls0 = __shfl(s0, src, 64);
+        const long long lend = ls0 + (long long)__shfl(len, src, 64);
+        const long long w_lo = ls0 >> 1, w_hi = (lend - 1) >> 1;            // the words that hold a sample of the event
+        EventAcc B{0, 0, 32767, -32768};
+        for (long long wb = w_lo; wb <= w_hi; wb += 64) {
+            const long long w = wb + lane;
+            if (w <= w_hi) {
+                const uint32_t x = W[w];
+                if (2 * w >= ls0) B.take(x);                                // (2 w < lend: w <= w_hi)
+                if (2 * w + 1 < lend) B.take(x >> 16);                      // (2 w + 1 >= ls0: w >= w_lo)
+            }
+        }
+#pragma unroll
+        for (int d = 32; d; d >>= 1) {
+            B.sum += __shfl_xor(B.sum, d, 64); B.sq += __shfl_xor(B.sq, d, 64);
+            B.mn = min(B.mn, __shfl_xor(B.mn, d, 64)); B.mx = max(B.mx, __shfl_xor(B.mx, d, 64));
+        }
+        if (lane == src) A = B;
+    }
+    return A;
+}
+
+// mean / sd of an event of read r from its sums, as include/sqg_events.h states them: one rounding per operation (the build has
+// -ffp-contract=off); double sqrt is correctly rounded on this device, as the exact sample path relies on (k_common.h: box_muller_exact)
+template <bool PA>
+__device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, const int len, const EventAcc& A, float* mean, float* sd) {
+    const double dl = (double)len, ds = (double)A.sum;
+    const double m = ds / dl;
+    double v = ((double)A.sq - ds * m) / dl;
+    v = v < 0 ? 0 : v;
+    const double s = sqrt(v);
+    if (PA) {
+        const double offset = Q.reads[r].offset;
+        *mean = (float)(((m + offset) * Q.range) / Q.dig);
+        *sd = (float)((s * Q.range) / Q.dig);
+    } else {
+        const float2 cs = Q.consts[r];                                   // cs.x = med2 / 2 exactly: |med2| < 2^17
+        *mean = (float)((m - (double)cs.x) * (double)cs.y);
+        *sd = (float)(s * (double)cs.y);
+    }
+}
+
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_evtab_reduce(EventParams Q) {
     const int lane = threadIdx.x & 63;
@@ -89,61 +147,15 @@ __global__ __launch_bounds__(CHUNK_WG) void k_evtab_reduce(EventParams Q) {
             len = Q.dwell ? (int)Q.dwell[i] : Q.const_sps;
             s0 = Q.sig_off[r] + Q.ev_start[i];
         }
-        EventAcc A{0, 0, 32767, -32768};
-        if (have && len <= EVT_LANE_MAX) {
-            long long s = s0;
-            const long long end = s0 + len;
-            if ((s & 1) && s < end) { A.take(W[s >> 1] >> 16); s++; }
-            for (; s + 2 <= end; s += 2) { const uint32_t w = W[s >> 1]; A.take(w); A.take(w >> 16); }
-            if (s < end) A.take(W[s >> 1]);
-        }
-        // the long events of this wavefront, one at a time by all of its lanes: `todo`, `ls0` and `lend` are the same in every lane
-        unsigned long long todo = __ballot(have && len > EVT_LANE_MAX);
-        while (todo) {
-            const int src = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const long long ls0 = __shfl(s0, src, 64);
-            const long long lend = ls0 + (long long)__shfl(len, src, 64);
-            const long long w_lo = ls0 >> 1, w_hi = (lend - 1) >> 1;            // the words that hold a sample of the event
-            EventAcc B{0, 0, 32767, -32768};
-            for (long long wb = w_lo; wb <= w_hi; wb += 64) {
-                const long long w = wb + lane;
-                if (w <= w_hi) {
-                    const uint32_t x = W[w];
-                    if (2 * w >= ls0) B.take(x);                                // (2 w < lend: w <= w_hi)
-                    if (2 * w + 1 < lend) B.take(x >> 16);                      // (2 w + 1 >= ls0: w >= w_lo)
-                }
-            }
-#pragma unroll
-            for (int d = 32; d; d >>= 1) {
-                B.sum += __shfl_xor(B.sum, d, 64); B.sq += __shfl_xor(B.sq, d, 64);
-                B.mn = min(B.mn, __shfl_xor(B.mn, d, 64)); B.mx = max(B.mx, __shfl_xor(B.mx, d, 64));
-            }
-            if (lane == src) A = B;
-        }
+        const EventAcc A = evtab_take(W, have, len, s0, lane);
         if (!have) continue;
         if (Q.sum) Q.sum[i] = A.sum;
         if (Q.sumsq) Q.sumsq[i] = (long long)A.sq;
         if (Q.vmin) Q.vmin[i] = (int16_t)A.mn;
         if (Q.vmax) Q.vmax[i] = (int16_t)A.mx;
         if (Q.mean || Q.sd) {
-            // include/sqg_events.h: one rounding per operation (the build has -ffp-contract=off); double sqrt is correctly rounded on this
-            // device, as the exact sample path relies on (k_common.h: box_muller_exact)
-            const double dl = (double)len, ds = (double)A.sum;
-            const double m = ds / dl;
-            double v = ((double)A.sq - ds * m) / dl;
-            v = v < 0 ? 0 : v;
-            const double s = sqrt(v);
             float mean, sd;
-            if (PA) {
-                const double offset = Q.reads[r].offset;
-                mean = (float)(((m + offset) * Q.range) / Q.dig);
-                sd = (float)((s * Q.range) / Q.dig);
-            } else {
-                const float2 cs = Q.consts[r];                                   // cs.x = med2 / 2 exactly: |med2| < 2^17
-                mean = (float)((m - (double)cs.x) * (double)cs.y);
-                sd = (float)(s * (double)cs.y);
-            }
+            evtab_derive<PA>(Q, r, len, A, &mean, &sd);
             if (Q.mean) Q.mean[i] = mean;
             if (Q.sd) Q.sd[i] = sd;
         }

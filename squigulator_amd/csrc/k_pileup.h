@@ -1,0 +1,86 @@
+// k_pileup.h -- the events of a batch added, across reads, into per-key sums the caller keeps from batch to batch (include/sqg_pileup.h)
+// Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_events_table.h, whose scan pass and sample reduction it uses.
+//
+//   k_pileup<PA>   k_evtab_reduce's grid: a flat grid over the batch's events, one event per lane, the samples taken by evtab_take and mean / sd
+//                  derived by evtab_derive -- the very code of the event table, so q(mean) is q of the float the table holds.  Whether an event
+//                  counts and where is decided BEFORE its samples are loaded: an event outside the key window costs its descriptor and no sample.
+//                  No per-event column is written.  The adds are no-return relaxed integer atomics at agent scope; consecutive lanes hold
+//                  consecutive events of one read, hence consecutive keys (BY_REF), so a wave's atomic instruction touches one run of 256 B
+//                  (n) or 512 B (the 64-bit sums).  Integer adds commute: the sums do not depend on the order the events arrive in.
+//                  counted / outside: a ballot per wavefront, one atomic each from its first lane into a 16-byte counter block.
+#pragma once
+
+struct PileRead { long long key0; int first, L, step; };      // origin; the insert's first base within chain 0, its bases (0: a stand-in read); +1 / -1 / 0
+
+struct PileupParams {
+    const PileRead* pr;                                       // [n_reads]
+    const uint32_t* kmer; const uint8_t* seg;                 // [n_events] of the scan pass; null where neither key nor split needs them
+    int by_kmer, split_strand, split_meth, k;
+    unsigned int segs;
+    long long lo, hi;
+    unsigned int* n; long long *dwell, *dwell_sq, *mean_sum, *mean_sq, *sd_sum;   // the caller's [planes][hi - lo], may be null
+    unsigned long long* stat;                                 // {counted, outside}
+};
+
+__device__ __forceinline__ long long pileup_q(const float x) { return (long long)rint((double)x * 4096.0); }
+
+template <bool PA>
+__global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams U) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.sig);
+    const long long width = U.hi - U.lo;
+    const bool want_samples = U.mean_sum || U.mean_sq || U.sd_sum;
+    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
+        const long long i = base + threadIdx.x;
+        const bool have = i < Q.n_events;
+        int r = 0, len = 0;
+        long long s0 = 0, key = 0;
+        bool eligible = false;
+        int plane = 0;
+        if (have) {
+            r = Q.ev_read[i];
+            len = Q.dwell ? (int)Q.dwell[i] : Q.const_sps;
+            s0 = Q.sig_off[r] + Q.ev_start[i];
+            const PileRead pr = U.pr[r];
+            if (U.by_kmer) {
+                eligible = pr.step != 0 && ((U.segs >> U.seg[i]) & 1u);
+                key = (long long)U.kmer[i];
+            } else {
+                const ReadDesc rd = Q.reads[r];
+                const long long e = i - rd.ev_off;
+                const long long j = e - pr.first;
+                eligible = pr.step != 0 && e < rd.ne0 && j >= 0 && j <= (long long)pr.L - U.k;
+                key = pr.key0 + (long long)pr.step * j;
+            }
+            if (U.split_strand) plane = pr.step < 0 ? 1 : 0;
+            if (U.split_meth && eligible) {
+                bool m = false;
+                uint32_t x = U.kmer[i];
+                for (int q = 0; q < U.k; q++) { m |= x % 5u == 3u; x /= 5u; }
+                plane += m ? (U.split_strand ? 2 : 1) : 0;
+            }
+        }
+        const bool inside = eligible && key >= U.lo && key < U.hi;
+        // (every lane of the wavefront is here: evtab_take and the ballots are wave-wide)
+        const EventAcc A = evtab_take(W, inside && want_samples && len > 0, len, s0, lane);
+        const unsigned long long m_in = __ballot(inside), m_out = __ballot(eligible && !inside);
+        if (lane == 0) {
+            if (m_in) __hip_atomic_fetch_add(U.stat, (unsigned long long)__popcll(m_in), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (m_out) __hip_atomic_fetch_add(U.stat + 1, (unsigned long long)__popcll(m_out), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (!inside) continue;
+        const long long at = (long long)plane * width + (key - U.lo);
+        if (U.n) __hip_atomic_fetch_add(U.n + at, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (len <= 0) continue;                                                   // no sample, no mean: n only
+        if (U.dwell) __hip_atomic_fetch_add(U.dwell + at, (long long)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (U.dwell_sq) __hip_atomic_fetch_add(U.dwell_sq + at, (long long)len * len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (want_samples) {
+            float mean, sd;
+            evtab_derive<PA>(Q, r, len, A, &mean, &sd);
+            const long long qm = pileup_q(mean);
+            if (U.mean_sum) __hip_atomic_fetch_add(U.mean_sum + at, qm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (U.mean_sq) __hip_atomic_fetch_add(U.mean_sq + at, (long long)((unsigned long long)qm * (unsigned long long)qm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (U.sd_sum) __hip_atomic_fetch_add(U.sd_sum + at, pileup_q(sd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}

@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h and k_events_table.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h and k_pileup.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -20,6 +20,7 @@
 //   k_site_*      the CpG sites of every read from the dwell scan, then a normalised window, the bases around it and their places in the window per site (include/sqg_sites.h)
 //   k_evtab_*     the per-event table: every event's place, segment, k-mer and level from the dwell scan, then a flat segmented reduction of the int16 signal by event
 //                 (sum, sum of squares, min, max; mean / sd in FP64), long events by a whole wavefront (include/sqg_events.h)
+//   k_pileup      the same events added across reads into per-key integer sums the caller keeps: scatter-accumulate by no-return integer atomics (include/sqg_pileup.h)
 //   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
@@ -47,3 +48,4 @@
 #include "k_segments.h"
 #include "k_sites.h"
 #include "k_events_table.h"
+#include "k_pileup.h"
