@@ -397,7 +397,11 @@ def test_level_shift_window_reaching_into_the_inserts(cid, sps, monkeypatch):
     lowered = plain["clean_raw"] != _cpu(tg.clean_raw)
     assert lowered.any() and not lowered.all()              # some samples were lowered, some were not
     for L2, S2 in ((64, 8), (72, 200), (4096, 4099)):      # rows that start anywhere in the window; more than one 64-sample step per chunk
-        _check(b, reads, mean, k, rna, meth, prefix, o.profile, L2, S2, 16, [("f16", "medmad")], f"{cid} sps {sps} L {L2}", sps=sps)
+        _, ch2, tg2 = _check(b, reads, mean, k, rna, meth, prefix, o.profile, L2, S2, 16, [("f16", "medmad")], f"{cid} sps {sps} L {L2}", sps=sps)
+        if (L2, S2) == (64, 8):                             # k_target_shift's grid is min(n_chunks, 4096) workgroups: chunks behind it are met on a second trip
+            plain = SR.batch_targets_trimmed(reads, mean, k, rna, meth, prefix, int(o.profile.dwell_mean), L2, S2, "f16", "medmad", o.profile.range, o.profile.digitisation)
+            lowered = (plain["clean_raw"] != _cpu(tg2.clean_raw)).any(axis=1)
+            assert ch2.n_chunks > 4096 and lowered[4096:].any() and lowered[:4096].any()
     b.free(); gen.close()
 
 
