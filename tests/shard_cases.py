@@ -1,0 +1,428 @@
+"""The jobs and drivers of tests/test_sharded_consumers.py: batches made the two ways several GPUs make them -- range sharding
+(sqg_set_range_mode, sqg_batch_sample_range or sqg_skip_reads, sqg_batch_run_begin / _end) and worker sharding (worker_lo / worker_hi, a
+worker[] array) -- and what the consumer calls of include/sqg_*.h must produce on them: the numpy references of the single-context test
+files, fed with the reads of the oracle's single-process run that a rank holds.  Not collected."""
+import numpy as np
+
+import chunks_ref as R
+import events_ref as EV
+import events_vec as VEC
+import orc
+import pileup_ref as PR
+import segments_ref as SR
+import sites_ref as S
+import targets_ref as T
+from squigulator_amd import api, model, profiles, shard
+from test_range_sharding import MFREQ_DENSE, Hip, _ranges
+from test_sampler import NCOV, SEQUIN, _contigs
+
+SEED = 42
+CHUNK = (512, 256, 128)                                     # chunk_len, stride, max_label
+CHUNK_SETTINGS = (("f16", "medmad"), ("f32", "pa"))
+SITE_GEOMETRIES = ((256, 128), (64, 32))                    # (win_len, before); the focus is (k + 1) // 2
+EVENT_SETTINGS = (("pa", False), ("medmad", False), ("pa", True), ("medmad", True))
+KEY_BASE = (1 << 40) + 12345                                # the caller's origin of the staged jobs: keys past 32 bits
+METH_LETTERS = b"ACGTM" + b"ACGTM" + b"ACGTM" + b"mN"
+
+# name -> the job.  kind: the driver; empty: the (batch, rank) pairs that hold no read on purpose; short: (batch, read, bases) of the reads cut
+# to less than a k-mer -- the drawn lengths (40 ... 873 bases) hold none: batch 0 (ranges [0, 5) and [5, 11)) has one as the first and one as
+# the last read of either rank, batch 1 (ranges [0, 3) and [3, 6)) one as the last read of rank 0 and one as the first of rank 1.
+# expect: what the oracle and sites_ref give on the CPU (test_the_jobs_hold_what_can_go_wrong asserts it): per batch
+# (sites, sites with label 1, dropped candidates, sites per rank, positions keyed by reads of two different ranks)
+JOBS = {
+    "r9_meth_g3": dict(kind="range_sampled", profile="dna-r9-prom", meth=True, fasta=NCOV, rlen=900, T=1, G=3, batches=[9, 2], empty={(1, 0)},
+                       strands=["-+-++----", None], expect=[(124, 17, 2, [75, 10, 39], 454), (29, None, None, [0, 15, 14], None)]),
+    "r9_meth_t2_g3": dict(kind="range_sampled", profile="dna-r9-prom", meth=True, fasta=NCOV, rlen=900, T=2, G=3, batches=[12],
+                          expect=[(157, 20, 2, None, 748)]),
+    "r10_g2": dict(kind="range_sampled", profile="dna-r10-prom", fasta=NCOV, rlen=700, T=1, G=2, batches=[10], expect=[(118, 0, 4, None, 349)]),
+    "r10_g2_meth": dict(kind="range_sampled", profile="dna-r10-prom", meth=True, fasta=NCOV, rlen=700, T=1, G=2, batches=[10],
+                        expect=[(118, 13, 4, None, 349)]),
+    # (with batches [8, 9] no transcript position is keyed by reads of both ranks, nor with a second batch of up to 20 reads: 22 is the first
+    # size that has one -- 4393 positions; the first batch has none)
+    "rna004_prefix_g2": dict(kind="range_sampled", profile="rna004-prom", flags=profiles.SQ_PREFIX, fasta=SEQUIN, rlen=10000, sample=api.SAMPLE_RNA,
+                             T=1, G=2, batches=[8, 22], exact=True, shared=[0, 4393]),
+    "staged_t2_g2": dict(kind="range_staged", profile="dna-r9-prom", k=6, T=2, G=2, letters=b"ACGT", sizes=(11, 6), lengths=(5, 900), reads_seed=3, shared=[128, 177], short=((0, 0, 1), (0, 4, 5), (0, 5, 3), (0, 10, 2), (1, 2, 4), (1, 3, 5))),
+    "staged_t2_g2_meth": dict(kind="range_staged", profile="dna-r9-prom", k=6, meth=True, T=2, G=2, letters=METH_LETTERS, sizes=(11, 6),
+                              lengths=(5, 900), reads_seed=3, shared=[128, 177], short=((0, 0, 1), (0, 4, 5), (0, 5, 3), (0, 10, 2), (1, 2, 4), (1, 3, 5))),
+    # one context in range mode, four batches of as many reads: tests/test_sharded_consumers.py's lifetime test
+    "lifetime_g1": dict(kind="range_staged", profile="dna-r9-prom", k=6, meth=True, T=1, G=1, letters=METH_LETTERS, sizes=(5, 5, 5, 5), lengths=(500, 900), reads_seed=17),
+    "workers_t4_g2": dict(kind="worker_staged", profile="dna-r9-prom", T=4, G=2, letters=b"ACGT", sizes=(24, 24, 24), lengths=(300, 2500), reads_seed=31),
+    "workers_t6_g3": dict(kind="worker_staged", profile="dna-r10-prom", T=6, G=3, letters=b"ACGT", sizes=(18, 18, 18), lengths=(300, 2500), reads_seed=31),
+    "workers_t4_g2_sampled": dict(kind="worker_sampled", profile="dna-r9-prom", fasta=NCOV, rlen=1200, T=4, G=2, batches=[24, 24, 24]),
+    "workers_t6_g3_sampled": dict(kind="worker_sampled", profile="dna-r10-prom", fasta=NCOV, rlen=1200, T=6, G=3, batches=[18, 18, 18]),
+}
+
+
+class Setup:
+    """what a job's contexts are created with, and what the references need to know of them"""
+
+    def __init__(self, name, extra_flags=0):
+        j = JOBS[name]
+        self.name, self.job = name, j
+        self.prof, fl = profiles.get_profile(j["profile"])
+        self.meth = bool(j.get("meth"))
+        self.flags = fl | j.get("flags", 0) | (profiles.SQ_METH if self.meth else 0) | extra_flags
+        self.k = j.get("k") or profiles.default_kmer_size(self.flags)
+        self.mean, self.stdv = model.synthetic_model(self.k, meth=self.meth)
+        self.rna, self.prefix = bool(self.flags & profiles.SQ_RNA), bool(self.flags & profiles.SQ_PREFIX)
+        self.sps = int(self.prof.dwell_mean)
+        self.T, self.G = j["T"], j["G"]
+        self.sampled = j["kind"] in ("range_sampled", "worker_sampled")
+        self.by_worker = j["kind"] in ("worker_staged", "worker_sampled")
+        self.sites = not self.rna and not self.prefix
+        self.focus = (self.k + 1) // 2
+        self.n_rows = self.T * len(self.mean)
+        self.contigs = self.names = None
+
+    def generator(self, mode=api.MODE_CERTIFIED, worker_lo=0, worker_hi=None):
+        g = api.SignalGenerator(self.prof, self.flags, self.k, self.mean, self.stdv, SEED, num_workers=self.T, mode=mode, worker_lo=worker_lo, worker_hi=worker_hi)
+        if self.sampled:
+            self.oracle_job()                               # (the contigs as the oracle loaded them)
+            g.load_genome(self.contigs, self.job["rlen"], self.job.get("sample", api.SAMPLE_DNA))
+            if self.meth:
+                g.set_meth(self.contigs, self.names, MFREQ_DENSE)
+        return g
+
+    # ---- the job on the CPU
+    def staged_reads(self):
+        j = self.job
+        rng = np.random.default_rng(j["reads_seed"])
+        out = [[bytes(rng.choice(list(j["letters"]), int(m)).astype(np.uint8)) for m in rng.integers(*j["lengths"], nb)] for nb in j["sizes"]]
+        for bi, i, m in j.get("short", ()):                 # reads shorter than a k-mer: the first m bases of the read drawn at that place
+            assert 1 <= m < self.k
+            out[bi][i] = out[bi][i][:m]
+        return out
+
+    def workers_of(self, n):
+        """the worker of every read of a batch of n: the reference's static partition"""
+        return shard.batch_workers(n, self.T)
+
+    def oracle_job(self):
+        """the oracle's single-process run of the whole job -> per batch dict(reads [dict(sig, ss, seq, offset)], key0, step, lens, strand)"""
+        if (self.name, self.flags) in _ORACLE:
+            self.contigs, self.names = _ORACLE[(self.name, self.flags)][1:]
+            return _ORACLE[(self.name, self.flags)][0]
+        j = self.job
+        orac = orc.Oracle(self.prof, self.flags, self.k, self.mean, self.stdv, SEED, num_workers=self.T, rlen=j.get("rlen", 10000))
+        out = []
+        if self.sampled:
+            ref = orac.load_ref(j["fasta"], None, MFREQ_DENSE if self.meth else None)
+            self.contigs, self.names = _contigs(ref), [ref.names[i].decode() for i in range(ref.num_ref)]
+            off = np.concatenate(([0], np.cumsum([len(c) for c in self.contigs])))
+            for nb in j["batches"]:
+                rs = orac.run_batch(nb)
+                strand = "".join(r.strand for r in rs).encode()
+                key0, step = PR.sampler_origin(off, [r.ref_idx for r in rs], [r.ref_pos_st for r in rs], [r.rlen for r in rs], strand, self.k)
+                out.append(dict(reads=[dict(sig=r.sig, ss=r.ss, seq=r.seq, offset=r.offset) for r in rs], key0=key0, step=step, strand=strand.decode()))
+        else:
+            rng = np.random.default_rng(j["reads_seed"] + 1000)
+            for bt in self.staged_reads():
+                rs = orac.run_batch_assigned(bt, self.workers_of(len(bt)))
+                n = len(bt)
+                # the caller's origin: every read laid somewhere on a span of 2000 keys, so that reads of different ranks meet; the steps go
+                # round -1, 0, +1 from a drawn start, so that every rank that holds three reads or more has all three values
+                step = ((np.arange(n) + int(rng.integers(0, 3))) % 3 - 1).astype(np.int8)
+                key0 = KEY_BASE + rng.integers(0, 2000, n).astype(np.int64)
+                out.append(dict(reads=[dict(sig=r.sig, ss=r.ss, seq=s, offset=r.offset) for r, s in zip(rs, bt)], key0=key0, step=step, strand=None))
+        for o in out:
+            o["lens"] = np.array([len(r["seq"]) for r in o["reads"]], np.int64)
+        orac.close()
+        _ORACLE[(self.name, self.flags)] = (out, self.contigs, self.names)
+        return out
+
+    def rank_reads(self, n, g):
+        """the indices in a batch of n reads of the reads rank g holds"""
+        if self.by_worker:
+            return shard.shard_batch(n, self.T, g, self.G)[0]
+        lo, hi = _ranges(n, self.G)[g]
+        return np.arange(lo, hi)
+
+    def window(self):
+        """[lo, hi) of the job's by-position keys: the loaded genome, or the span the caller's origin lays the staged reads on"""
+        if self.sampled:
+            self.oracle_job()
+            return 0, sum(len(c) for c in self.contigs)
+        return KEY_BASE - 3000, KEY_BASE + 5000
+
+    def pile_cfgs(self):
+        """name -> (new_pileup's keywords, norm, trim): the configurations of the pileups that must add up"""
+        out = {}
+        lo, hi = self.window()
+        out["ref_split"] = (dict(by="ref", split=("strand", "meth") if self.meth else ("strand",), lo=lo, hi=hi), "pa", False)
+        keys = np.sort(np.concatenate([self.keys(o, np.arange(len(o["reads"]))) for o in self.oracle_job()]))
+        out["ref_window"] = (dict(by="ref", lo=int(keys[len(keys) // 4]) + 1, hi=int(keys[3 * len(keys) // 4])), "medmad", False)
+        if self.prefix:
+            out["kmer_segs"] = (dict(by="kmer", segs=(0, 1, 2, 3)), "medmad", True)
+        return out
+
+    def keys(self, o, idx):
+        """the by-position keys of the events of reads idx of the oracle's batch o that count"""
+        ev_off = np.concatenate(([0], np.cumsum([len(o["reads"][i]["ss"]) for i in idx]))).astype(np.int64)
+        ev = dict(ev_read=np.repeat(np.arange(len(idx)), np.diff(ev_off)))
+        ok, key, _ = PR.eligible_and_key(ev, ev_off, o["key0"][idx], o["step"][idx], o["lens"][idx], self.k, self.rna, self.prefix)
+        return key[ok]
+
+    # ---- the references, as groups: name -> dict(off [n_reads + 1], read [rows], rows {key: [rows, ...]}, per_read {key: [n_reads]})
+    def expected(self, reads, threaded=False):
+        p, k, rna, meth, prefix, sps, mean = self.prof, self.k, self.rna, self.meth, self.prefix, self.sps, self.mean
+        L, St, W = CHUNK
+        n = len(reads)
+        out = {}
+        for dtype, norm in CHUNK_SETTINGS[:1] if threaded else CHUNK_SETTINGS:
+            fdt = np.float16 if dtype == "f16" else np.float32
+            if n == 0:
+                w = dict(signal=np.zeros((0, L), fdt), labels=np.zeros((0, W), np.uint8), label_len=np.zeros(0, np.int32), chunk_start=np.zeros(0, np.int64),
+                         chunk_read=np.zeros(0, np.int32), med2=np.zeros(0, np.int32), mad4=np.zeros(0, np.int32), chunk_off=np.zeros(1, np.int64))
+                t = dict(clean=np.zeros((0, L), fdt), clean_raw=np.zeros((0, L), np.int16), moves=np.zeros((0, L), np.uint8), kmer=np.zeros((0, L), np.uint32))
+            elif prefix:
+                w = SR.batch_chunks_trimmed(reads, k, rna, meth, prefix, sps, L, St, W, dtype, norm, p.range, p.digitisation)
+                t = None if threaded else SR.batch_targets_trimmed(reads, mean, k, rna, meth, prefix, sps, L, St, dtype, norm, p.range, p.digitisation)
+            else:
+                w = R.batch_chunks(reads, k, rna, meth, L, St, W, dtype, norm, p.range, p.digitisation)
+                t = None if threaded else T.batch_targets(reads, mean, k, rna, meth, L, St, dtype, norm, p.range, p.digitisation)
+            out[f"chunks {dtype} {norm}"] = dict(off=w["chunk_off"], read=w["chunk_read"], rows={key: w[key] for key in ("signal", "labels", "label_len", "chunk_start")},
+                                                 per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+            if t is not None:
+                assert n == 0 or np.array_equal(t["chunk_off"], w["chunk_off"])
+                out[f"targets {dtype} {norm}"] = dict(off=w["chunk_off"], read=w["chunk_read"], rows={key: t[key] for key in ("clean", "clean_raw", "moves", "kmer")}, per_read={})
+        if self.sites:
+            for Lw, before in SITE_GEOMETRIES[:1] if threaded else SITE_GEOMETRIES:
+                w = S.batch_sites(reads, k, meth, S.Cfg(Lw, before, self.focus, 21, 10, "f16", "medmad"), p.range, p.digitisation)
+                out[f"sites {Lw}"] = dict(off=w["site_off"], read=w["site_read"], rows={key: w[key] for key in S.KEYS if key != "site_read"},
+                                          per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+        for norm, trim in EVENT_SETTINGS[:1] if threaded else EVENT_SETTINGS:
+            w = EV.batch_events(reads, mean, k, rna, meth, prefix, sps, norm, trim, p.range, p.digitisation)
+            out[f"events {norm} {int(trim)}"] = dict(off=w["ev_off"], read=w["ev_read"], rows={key: w[key] for key in EV.PER_EVENT if key != "ev_read"},
+                                                    per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+        if prefix and not threaded:
+            seg, shift = SR.batch_segments(reads, k, rna, prefix, sps)
+            out["segments"] = dict(off=np.arange(n + 1, dtype=np.int64), read=np.arange(n, dtype=np.int32), rows=dict(seg=seg, shift=shift), per_read={})
+        return out
+
+    def expected_sites(self, reads):
+        """sites_ref at the first geometry: window 256, 128 samples in front of the anchor event"""
+        Lw, before = SITE_GEOMETRIES[0]
+        return S.batch_sites(reads, self.k, self.meth, S.Cfg(Lw, before, self.focus, 21, 10, "f16", "medmad"), self.prof.range, self.prof.digitisation)
+
+    def pileup_table(self, reads, norm, trim, need_kmer):
+        """the per-event columns pileup_ref takes: events_ref's, or -- where neither the key nor a split needs k-mer and segment -- the
+        vectorised rows that tests/test_event_grids.py pins to it"""
+        p = self.prof
+        if need_kmer or trim or self.prefix:
+            return EV.batch_events(reads, self.mean, self.k, self.rna, self.meth, self.prefix, self.sps, norm, trim, p.range, p.digitisation)
+        sig = np.concatenate([r["sig"] for r in reads]) if reads else np.zeros(0, np.int16)
+        dw = np.concatenate([np.asarray(r["ss"]) for r in reads]) if reads else np.zeros(0, np.int64)
+        sig_off = np.concatenate(([0], np.cumsum([len(r["sig"]) for r in reads]))).astype(np.int64)
+        ev_off = np.concatenate(([0], np.cumsum([len(r["ss"]) for r in reads]))).astype(np.int64)
+        w = VEC.batch_rows(sig, sig_off, dw, ev_off, [r["offset"] for r in reads], self.rna, norm, p.range, p.digitisation,
+                           stats=[R.stats(np.asarray(r["sig"], np.int16)) for r in reads] if norm != "pa" else None)
+        w["ev_off"] = ev_off
+        return w
+
+    def expected_pileup(self, kw, norm, trim):
+        """pileup_ref over the whole job, batch after batch into the same sums -> (the six arrays, counted, outside)"""
+        by = PR.BY_KMER if kw["by"] == "kmer" else PR.BY_REF
+        split = sum({"strand": PR.SPLIT_STRAND, "meth": PR.SPLIT_METH}[s] for s in kw.get("split", ()))
+        segs = sum(1 << q for q in kw.get("segs", ()))
+        lo, hi = (kw["lo"], kw["hi"]) if by == PR.BY_REF else (0, len(self.mean))
+        into, counted, outside = None, 0, 0
+        for o in self.oracle_job():
+            ev = self.pileup_table(o["reads"], norm, trim, by == PR.BY_KMER or bool(split & PR.SPLIT_METH))
+            into, c, x = PR.pileup(ev, ev["ev_off"], o["key0"], o["step"], o["lens"], self.k, self.rna, self.prefix, by, split, segs, lo, hi, into)
+            counted += c; outside += x
+        return into, counted, outside
+
+    # ---- the consumer calls of a batch, as the same groups
+    def consume(self, b, threaded=False):
+        L, St, W = CHUNK
+        trim = self.prefix
+        out = {}
+        cpu = _host
+        for dtype, norm in CHUNK_SETTINGS[:1] if threaded else CHUNK_SETTINGS:
+            ch = b.chunks(L, St, W, dtype=dtype, norm=norm, trim=trim)
+            plan, nc = b.chunk_plan(L, St, trim=trim)
+            assert nc == ch.n_chunks == len(ch.chunk_read) and plan[-1] == nc
+            out[f"chunks {dtype} {norm}"] = dict(off=ch.chunk_off, plan=plan, read=cpu(ch.chunk_read), rows={key: cpu(getattr(ch, key)) for key in ("signal", "labels", "label_len", "chunk_start")},
+                                                 per_read=dict(med2=cpu(ch.med2), mad4=cpu(ch.mad4)))
+            if not threaded:
+                tg = b.chunk_targets(L, St, dtype=dtype, norm=norm, clean=True, clean_raw=True, moves=True, kmer=True, trim=trim)
+                assert tg.n_chunks == nc
+                out[f"targets {dtype} {norm}"] = dict(off=tg.chunk_off, read=cpu(ch.chunk_read), rows={key: cpu(getattr(tg, key), key) for key in ("clean", "clean_raw", "moves", "kmer")}, per_read={})
+        if self.sites:
+            for Lw, before in SITE_GEOMETRIES[:1] if threaded else SITE_GEOMETRIES:
+                st = b.sites(Lw, before, self.focus, 21, 10, dtype="f16", norm="medmad")
+                plan, ns = b.site_plan(Lw, before, self.focus)
+                assert ns == st.n_sites
+                out[f"sites {Lw}"] = dict(off=st.site_off, plan=plan, read=cpu(st.site_read), rows={key: cpu(getattr(st, key)) for key in S.KEYS if key != "site_read"},
+                                          per_read=dict(med2=cpu(st.med2), mad4=cpu(st.mad4)))
+        for norm, tr in EVENT_SETTINGS[:1] if threaded else EVENT_SETTINGS:
+            ev = b.events(norm, tr)
+            assert ev.n_events == b.n_events
+            out[f"events {norm} {int(tr)}"] = dict(off=b.ev_off, read=cpu(ev.ev_read), rows={key: cpu(getattr(ev, key), key) for key in EV.PER_EVENT if key != "ev_read"},
+                                                  per_read=dict(med2=cpu(ev.med2), mad4=cpu(ev.mad4)))
+        if self.prefix and not threaded:
+            seg, shift = b.segments()
+            out["segments"] = dict(off=np.arange(b.n_reads + 1, dtype=np.int64), read=np.arange(b.n_reads, dtype=np.int32), rows=dict(seg=cpu(seg), shift=cpu(shift)), per_read={})
+        return out
+
+    def origin(self, o, idx):
+        """what Batch.pileup takes as origin= for reads idx of the oracle's batch o: nothing for a sampled batch -- the rank derives the keys
+        from its own range of the sampler's records --, the slice of the caller's origin for a staged one"""
+        return None if self.sampled else (o["key0"][idx], o["step"][idx])
+
+
+_ORACLE = {}                                                # (job name, flags) -> the oracle's run
+
+
+def _host(t, key=None):
+    """a tensor on the host; the k-mer columns as the uint32 they are"""
+    a = t.cpu().numpy()
+    return a.view(np.uint32) if key == "kmer" else a
+
+
+def assert_groups(got, want, what):
+    """every group of `got` against `want`, bit for bit (floats as integers)"""
+    assert set(got) == set(want), f"{what}: {sorted(got)} vs {sorted(want)}"
+    for name, g in got.items():
+        w = want[name]
+        np.testing.assert_array_equal(g["off"], w["off"], err_msg=f"{what}: {name}: the rows' offsets")
+        if "plan" in g:
+            np.testing.assert_array_equal(g["plan"], w["off"], err_msg=f"{what}: {name}: the plan call")
+        assert set(g["rows"]) == set(w["rows"]) and set(g["per_read"]) == set(w["per_read"]), f"{what}: {name}: {sorted(g['rows'])} {sorted(g['per_read'])}"
+        cols = [("read", g["read"], w["read"])] + [(key, g["rows"][key], w["rows"][key]) for key in w["rows"]] + [(key, g["per_read"][key], w["per_read"][key]) for key in w["per_read"]]
+        for key, a, e in cols:
+            assert a.shape == e.shape and a.dtype == e.dtype, f"{what}: {name}: {key} {a.shape} {a.dtype} vs {e.shape} {e.dtype}"
+            np.testing.assert_array_equal(R.bits(a), R.bits(e), err_msg=f"{what}: {name}: {key}")
+
+
+def restrict(groups, idx):
+    """the groups of a whole batch restricted to the reads idx (increasing) and renumbered: what the rank that holds them must produce"""
+    idx = np.asarray(idx, np.int64)
+    out = {}
+    for name, g in groups.items():
+        off = np.asarray(g["off"], np.int64)
+        rows = np.concatenate([np.arange(off[i], off[i + 1]) for i in idx]) if len(idx) else np.zeros(0, np.int64)
+        counts = off[idx + 1] - off[idx]
+        out[name] = dict(off=np.concatenate(([0], np.cumsum(counts))).astype(np.int64),
+                         read=np.repeat(np.arange(len(idx)), counts).astype(g["read"].dtype),
+                         rows={key: a[rows] for key, a in g["rows"].items()}, per_read={key: a[idx] for key, a in g["per_read"].items()})
+        assert np.array_equal(g["read"][rows], np.repeat(idx, counts))
+    return out
+
+
+def pile_arrays(p):
+    """the six arrays of a Pileup on the host (n as the uint32 it is)"""
+    return {n: (lambda a: a.view(np.uint32) if n == "n" else a)(getattr(p, n).cpu().numpy()) for n in api.PILEUP_OUTPUTS}
+
+
+# ---------------------------------------------------------------------------------------------------------- drivers (GPU)
+class RangeRanks:
+    """G contexts in range mode on one GPU; the one exchange step -- the per-stream sample counts -- goes through the host"""
+
+    def __init__(self, su, mode=api.MODE_CERTIFIED):
+        self.su, self.hip = su, Hip()
+        self.gens = [su.generator(mode) for _ in range(su.G)]
+        for g in self.gens:
+            g.set_range_mode(True)
+
+    def sample(self, nb):
+        return [self.gens[g].sample(nb, lo=lo, hi=hi) for g, (lo, hi) in enumerate(_ranges(nb, self.su.G))]
+
+    def stage(self, bt):
+        """reads staged from the host: every rank calls sqg_skip_reads for the reads in front of and behind its range"""
+        n = len(bt)
+        wk = np.array([self.gens[0].L.sqg_worker_of(i, n, self.su.T) for i in range(n)], np.int32)
+        assert np.array_equal(wk, self.su.workers_of(n))
+        lens = np.array([len(r) for r in bt], np.int64)
+        bs = []
+        for g, (lo, hi) in enumerate(_ranges(n, self.su.G)):
+            self.gens[g].skip_reads(lens[:lo], wk[:lo])
+            bs.append(self.gens[g].stage(bt[lo:hi], wk[lo:hi]))
+            self.gens[g].skip_reads(lens[hi:], wk[hi:])
+        return bs
+
+    def begin(self, bs):
+        return [self.hip.to_host(b.run_begin(), self.su.n_rows).astype(np.uint64) for b in bs]
+
+    def end(self, bs, counts):
+        zero = np.zeros(self.su.n_rows, np.uint64)
+        for g, b in enumerate(bs):
+            pb, pa = self.hip.to_device(sum(counts[:g], zero)), self.hip.to_device(sum(counts[g + 1:], zero))
+            b.run_end(pb, pa).wait()
+            self.hip.free(pb); self.hip.free(pa)
+
+    def close(self):
+        for g in self.gens:
+            g.close()
+
+
+def range_sampled(su, mode=api.MODE_CERTIFIED):
+    """yields (batch index, rank, the run batch, the indices of its reads in the job's batch): sample(nb, lo=, hi=), run_begin, the counts
+    exchanged, run_end"""
+    rk = RangeRanks(su, mode)
+    try:
+        for bi, nb in enumerate(su.job["batches"]):
+            bs = rk.sample(nb)
+            rk.end(bs, rk.begin(bs))
+            for g, b in enumerate(bs):
+                yield bi, g, b, su.rank_reads(nb, g)
+            for b in bs:
+                b.free()
+    finally:
+        rk.close()
+
+
+def range_staged(su, mode=api.MODE_CERTIFIED):
+    rk = RangeRanks(su, mode)
+    try:
+        for bi, bt in enumerate(su.staged_reads()):
+            bs = rk.stage(bt)
+            rk.end(bs, rk.begin(bs))
+            for g, b in enumerate(bs):
+                yield bi, g, b, su.rank_reads(len(bt), g)
+            for b in bs:
+                b.free()
+    finally:
+        rk.close()
+
+
+def worker_contexts(su, mode=api.MODE_CERTIFIED):
+    return [su.generator(mode, *shard.worker_range(g, su.G, su.T)) for g in range(su.G)]
+
+
+def worker_batch(su, gen, g, n, bt=None):
+    """rank g's part of a batch of n reads, staged (bt: the batch's reads) or sampled: (the staged batch, the indices of its reads)"""
+    idx, wk = shard.shard_batch(n, su.T, g, su.G)
+    return (gen.stage([bt[i] for i in idx], wk) if bt is not None else gen.sample(len(idx), workers=wk)), idx
+
+
+def worker_sharded(su, mode=api.MODE_CERTIFIED):
+    """one context per block of workers, driven one after the other; staged reads, or the sampler's for a sampled job"""
+    gens = worker_contexts(su, mode)
+    try:
+        batches = [(nb, None) for nb in su.job["batches"]] if su.sampled else [(len(bt), bt) for bt in su.staged_reads()]
+        for bi, (n, bt) in enumerate(batches):
+            for g, gen in enumerate(gens):
+                b, idx = worker_batch(su, gen, g, n, bt)
+                b.run().wait()
+                yield bi, g, b, idx
+                b.free()
+    finally:
+        for gen in gens:
+            gen.close()
+
+
+def single(su, mode=api.MODE_CERTIFIED):
+    """the same job on one plain context that owns every worker: yields (batch index, the run batch)"""
+    gen = su.generator(mode)
+    try:
+        batches = [(nb, None) for nb in su.job["batches"]] if su.sampled else [(len(bt), bt) for bt in su.staged_reads()]
+        for bi, (n, bt) in enumerate(batches):
+            b = (gen.sample(n) if bt is None else gen.stage(bt, su.workers_of(n))).run().wait()
+            yield bi, b
+            b.free()
+    finally:
+        gen.close()
+
+
+DRIVERS = dict(range_sampled=range_sampled, range_staged=range_staged, worker_staged=worker_sharded, worker_sampled=worker_sharded)
