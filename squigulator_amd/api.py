@@ -188,6 +188,49 @@ class Chunks:
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
+# the consumer calls by header: name -> what its arguments behind (context, batch) point to
+_PLAN = (C.c_int64, C.c_int64)
+_CONSUMER_EXPORTS = (
+    (EXPORTS_CHUNKS, {"sqg_chunk_plan": (CChunkCfg,) + _PLAN, "sqg_batch_chunks": (CChunkCfg, CChunkOut)}),
+    (EXPORTS_TARGETS, {"sqg_batch_chunk_targets": (CChunkCfg, CChunkTargets)}),
+    (EXPORTS_SEGMENTS, {"sqg_batch_segments": (CSegments,), "sqg_chunk_plan_trimmed": (CChunkCfg,) + _PLAN,
+                        "sqg_batch_chunks_trimmed": (CChunkCfg, CChunkOut), "sqg_batch_chunk_targets_trimmed": (CChunkCfg, CChunkTargets)}),
+    (EXPORTS_SITES, {"sqg_site_plan": (CSiteCfg,) + _PLAN, "sqg_batch_sites": (CSiteCfg, CSiteOut)}),
+    (EXPORTS_EVENTS, {"sqg_batch_events": (CEventCfg, CEventOut)}),
+    (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
+)
+
+_ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
+          "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}}
+
+
+def _enum(who, **given):
+    """the C values of dtype= / norm= / by= given by name or by number, in the order given; SqgError naming them all when one is unknown"""
+    vals = [_ENUMS[k].get(v, v) for k, v in given.items()]
+    if not all(isinstance(v, int) for v in vals):
+        raise SqgError(-1, who, f"unknown {' / '.join(given)} {' / '.join(repr(v) for v in given.values())}")
+    return [v & 0xffffffff for v in vals]
+
+
+def _need(L, export, header, who):
+    """the guard of a call the CPU backend lacks"""
+    if not hasattr(L, export):
+        raise SqgError(-1, who, f"this backend has no {export} (include/{header})")
+
+
+def _want(outputs, names, who):
+    """the set of output names asked for (None: all of them)"""
+    want = set(names if outputs is None else outputs)
+    if want - set(names):
+        raise SqgError(-1, who, f"unknown outputs {sorted(want - set(names))}")
+    return want
+
+
+def _ptrs(struct, tensors):
+    """the C struct of device addresses: NULL for an output not wanted or empty"""
+    return struct(*(t.data_ptr() if t is not None and t.numel() else None for t in tensors))
+
+
 _libs = {}                  # absolute path -> loaded library
 LOADED_PATH = None          # the library the last load_library() call opened (bench.py prints it with its hash)
 
@@ -299,34 +342,11 @@ def load_library(path: str | None = None):
     L.sqg_set_stage_threads.argtypes = [vp, C.c_int]
     L.sqg_build_info.restype = C.c_char_p
     L.sqg_build_info.argtypes = []
-    if all(hasattr(L, n) for n in EXPORTS_CHUNKS):
-        L.sqg_chunk_plan.restype = C.c_int
-        L.sqg_chunk_plan.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(i64), C.POINTER(i64)]
-        L.sqg_batch_chunks.restype = C.c_int
-        L.sqg_batch_chunks.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
-    if all(hasattr(L, n) for n in EXPORTS_TARGETS):
-        L.sqg_batch_chunk_targets.restype = C.c_int
-        L.sqg_batch_chunk_targets.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
-    if all(hasattr(L, n) for n in EXPORTS_SEGMENTS):
-        L.sqg_batch_segments.restype = C.c_int
-        L.sqg_batch_segments.argtypes = [vp, vp, C.POINTER(CSegments)]
-        L.sqg_chunk_plan_trimmed.restype = C.c_int
-        L.sqg_chunk_plan_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(i64), C.POINTER(i64)]
-        L.sqg_batch_chunks_trimmed.restype = C.c_int
-        L.sqg_batch_chunks_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkOut)]
-        L.sqg_batch_chunk_targets_trimmed.restype = C.c_int
-        L.sqg_batch_chunk_targets_trimmed.argtypes = [vp, vp, C.POINTER(CChunkCfg), C.POINTER(CChunkTargets)]
-    if all(hasattr(L, n) for n in EXPORTS_SITES):
-        L.sqg_site_plan.restype = C.c_int
-        L.sqg_site_plan.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(i64), C.POINTER(i64)]
-        L.sqg_batch_sites.restype = C.c_int
-        L.sqg_batch_sites.argtypes = [vp, vp, C.POINTER(CSiteCfg), C.POINTER(CSiteOut)]
-    if all(hasattr(L, n) for n in EXPORTS_EVENTS):
-        L.sqg_batch_events.restype = C.c_int
-        L.sqg_batch_events.argtypes = [vp, vp, C.POINTER(CEventCfg), C.POINTER(CEventOut)]
-    if all(hasattr(L, n) for n in EXPORTS_PILEUP):
-        L.sqg_batch_pileup.restype = C.c_int
-        L.sqg_batch_pileup.argtypes = [vp, vp, C.POINTER(CPileupCfg), C.POINTER(COrigin), C.POINTER(CPileupOut), C.POINTER(CPileupStat)]
+    for names, table in _CONSUMER_EXPORTS:                  # each header's calls, when the library has them (the CPU backend has none)
+        if all(hasattr(L, n) for n in names):
+            for n in names:
+                getattr(L, n).restype = C.c_int
+                getattr(L, n).argtypes = [vp, vp] + [C.POINTER(t) for t in table[n]]
     _libs[path] = L
     return L
 
@@ -549,20 +569,15 @@ class Batch:
         return torch.as_tensor(_View(self, int(self.res.d_signal), int(self.n_samples)), device=dev)
 
     def _chunk_cfg(self, chunk_len, stride, max_label, dtype, norm):
-        if not hasattr(self.gen.L, "sqg_batch_chunks"):
-            raise SqgError(-1, "chunks", "this backend has no sqg_batch_chunks (include/sqg_chunks.h)")
-        dt = {"f16": CHUNK_F16, "f32": CHUNK_F32}.get(dtype, dtype)
-        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
-        if not isinstance(dt, int) or not isinstance(nm, int):
-            raise SqgError(-1, "chunks", f"unknown dtype / norm {dtype!r} / {norm!r}")
-        return CChunkCfg(int(chunk_len), int(chunk_len if stride is None else stride), int(max_label), dt & 0xffffffff, nm & 0xffffffff)
+        _need(self.gen.L, "sqg_batch_chunks", "sqg_chunks.h", "chunks")
+        dt, nm = _enum("chunks", dtype=dtype, norm=norm)
+        return CChunkCfg(int(chunk_len), int(chunk_len if stride is None else stride), int(max_label), dt, nm)
 
     def _trimmed(self, name, trim):
         """the library call `name`, or with trim its counterpart of include/sqg_segments.h (which cuts the inserts and takes SQG_PREFIX contexts)"""
         if not trim:
             return name
-        if not hasattr(self.gen.L, "sqg_batch_segments"):
-            raise SqgError(-1, "segments", "this backend has no sqg_batch_segments (include/sqg_segments.h)")
+        _need(self.gen.L, "sqg_batch_segments", "sqg_segments.h", "segments")
         return name + "_trimmed"
 
     def segments(self):
@@ -573,7 +588,7 @@ class Batch:
         dev = torch.device("cuda", self.gen.device)
         seg = torch.zeros((self.n_reads, 5), dtype=torch.int64, device=dev)
         shift = torch.zeros((self.n_reads, 2), dtype=torch.int64, device=dev)
-        out = CSegments(*(t.data_ptr() if t.numel() else None for t in (seg, shift)))
+        out = _ptrs(CSegments, (seg, shift))
         torch.cuda.synchronize(dev)
         self.gen._chk(self.gen.L.sqg_batch_segments(self.gen.ctx, self.handle, C.byref(out)), "sqg_batch_segments")
         return seg, shift
@@ -597,7 +612,7 @@ class Batch:
         dev = torch.device("cuda", self.gen.device)
         new = lambda shape, dt: (torch.zeros if nc == 0 else torch.empty)(shape, dtype=dt, device=dev)   # noqa: E731
         def call(name, out, *tensors):
-            out = out(*(t.data_ptr() if t is not None and t.numel() else None for t in tensors))
+            out = _ptrs(out, tensors)
             torch.cuda.synchronize(dev)                     # (the allocator's pending work on these blocks, if any, before another stream writes them)
             name = self._trimmed(name, trim)
             self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), name)
@@ -632,8 +647,7 @@ class Batch:
         mad4 are passed in instead of being computed again.  trim=True: for the chunks of chunks(..., trim=True)
         (sqg_batch_chunk_targets_trimmed, include/sqg_segments.h)."""
         import torch
-        if not hasattr(self.gen.L, "sqg_batch_chunk_targets"):
-            raise SqgError(-1, "chunk_targets", "this backend has no sqg_batch_chunk_targets (include/sqg_targets.h)")
+        _need(self.gen.L, "sqg_batch_chunk_targets", "sqg_targets.h", "chunk_targets")
         cfg, off, nc, dev, new, call = self._chunk_job(chunk_len, stride, 0, dtype, norm, trim)
         row = lambda want, dt: new((nc, cfg.chunk_len), dt) if want else None           # noqa: E731
         tg = Chunks(n_chunks=nc, chunk_off=off, clean=row(clean, torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16),
@@ -650,15 +664,11 @@ class Batch:
         return tg
 
     def _site_cfg(self, win_len, before, focus, ctx_len, ctx_before, dtype, norm):
-        if not hasattr(self.gen.L, "sqg_batch_sites"):
-            raise SqgError(-1, "sites", "this backend has no sqg_batch_sites (include/sqg_sites.h)")
-        dt = {"f16": CHUNK_F16, "f32": CHUNK_F32}.get(dtype, dtype)
-        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
-        if not isinstance(dt, int) or not isinstance(nm, int):
-            raise SqgError(-1, "sites", f"unknown dtype / norm {dtype!r} / {norm!r}")
+        _need(self.gen.L, "sqg_batch_sites", "sqg_sites.h", "sites")
+        dt, nm = _enum("sites", dtype=dtype, norm=norm)
         L, B = int(win_len), int(ctx_len)
         return CSiteCfg(L, int(L // 2 if before is None else before), int(self.gen.kmer_size // 2 if focus is None else focus), B,
-                        int(B // 2 if ctx_before is None else ctx_before), dt & 0xffffffff, nm & 0xffffffff)
+                        int(B // 2 if ctx_before is None else ctx_before), dt, nm)
 
     def site_plan(self, win_len: int, before: int | None = None, focus: int | None = None):
         """(site_off [n_reads+1], n_sites): the first CpG site of every read for windows of win_len samples, `before` of them in front of
@@ -681,9 +691,7 @@ class Batch:
         before / focus / ctx_before default to win_len / 2, k / 2, ctx_len / 2.  outputs: the names wanted (default all); the others are None."""
         import torch
         cfg = self._site_cfg(win_len, before, focus, ctx_len, ctx_before, dtype, norm)
-        want = set(SITE_OUTPUTS if outputs is None else outputs)
-        if want - set(SITE_OUTPUTS):
-            raise SqgError(-1, "sites", f"unknown outputs {sorted(want - set(SITE_OUTPUTS))}")
+        want = _want(outputs, SITE_OUTPUTS, "sites")
         off, ns = self._site_plan(cfg)                      # (validates all of cfg: the shapes below are sane)
         dev = torch.device("cuda", self.gen.device)
         L, B = cfg.win_len, cfg.ctx_len
@@ -692,7 +700,7 @@ class Batch:
                       context=((ns, B), torch.uint8), ctx_start=((ns, B + 1), torch.int32),
                       med2=((self.n_reads,), torch.int32), mad4=((self.n_reads,), torch.int32))
         st = Chunks(n_sites=ns, site_off=off, **{n: (torch.zeros(sh, dtype=dt, device=dev) if n in want else None) for n, (sh, dt) in shapes.items()})
-        out = CSiteOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(st, n) for n in SITE_OUTPUTS)))
+        out = _ptrs(CSiteOut, (getattr(st, n) for n in SITE_OUTPUTS))
         torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
         self.gen._chk(self.gen.L.sqg_batch_sites(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_sites")
         return st
@@ -705,15 +713,10 @@ class Batch:
         normalised by norm: "pa" or "medmad"); med2, mad4 [n_reads] (int32), over the whole read or with trim over its insert.
         outputs: the names wanted (default all); the others are None."""
         import torch
-        if not hasattr(self.gen.L, "sqg_batch_events"):
-            raise SqgError(-1, "events", "this backend has no sqg_batch_events (include/sqg_events.h)")
-        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
-        if not isinstance(nm, int):
-            raise SqgError(-1, "events", f"unknown norm {norm!r}")
-        want = set(EVENT_OUTPUTS if outputs is None else outputs)
-        if want - set(EVENT_OUTPUTS):
-            raise SqgError(-1, "events", f"unknown outputs {sorted(want - set(EVENT_OUTPUTS))}")
-        cfg = CEventCfg(nm & 0xffffffff, int(trim))
+        _need(self.gen.L, "sqg_batch_events", "sqg_events.h", "events")
+        nm, = _enum("events", norm=norm)
+        want = _want(outputs, EVENT_OUTPUTS, "events")
+        cfg = CEventCfg(nm, int(trim))
         if self.res is None and self.handle:
             r = CResult()                                   # (the row count; a batch that has not been run: the library's SQG_ESEQUENCE below)
             ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
@@ -724,7 +727,7 @@ class Batch:
                    kmer=torch.int32, level_raw=torch.int16, seg=torch.uint8, mean=torch.float32, sd=torch.float32, med2=torch.int32, mad4=torch.int32)
         ev = Chunks(n_events=ne, **{n: (torch.zeros(self.n_reads if n in ("med2", "mad4") else ne, dtype=dts[n], device=dev) if n in want else None)
                                     for n in EVENT_OUTPUTS})
-        out = CEventOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(ev, n) for n in EVENT_OUTPUTS)))
+        out = _ptrs(CEventOut, (getattr(ev, n) for n in EVENT_OUTPUTS))
         torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
         self.gen._chk(self.gen.L.sqg_batch_events(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_events")
         return ev
@@ -734,15 +737,14 @@ class Batch:
         (counted, outside).  origin=(key0, step): numpy arrays [n_reads] (int64, int8) in place of the sampler's origin -- for staged
         batches, or another coordinate system"""
         import torch
-        if not hasattr(self.gen.L, "sqg_batch_pileup"):
-            raise SqgError(-1, "pileup", "this backend has no sqg_batch_pileup (include/sqg_pileup.h)")
+        _need(self.gen.L, "sqg_batch_pileup", "sqg_pileup.h", "pileup")
         org = None
         if origin is not None:
             key0, step = np.ascontiguousarray(origin[0], np.int64), np.ascontiguousarray(origin[1], np.int8)
             if key0.shape != (self.n_reads,) or step.shape != (self.n_reads,):
                 raise SqgError(-1, "pileup", f"origin=(key0, step) must be two arrays of {self.n_reads} elements")
             org = COrigin(key0.ctypes.data_as(C.POINTER(C.c_int64)), step.ctypes.data_as(C.POINTER(C.c_int8)))
-        out = CPileupOut(*(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(p, n) for n in PILEUP_OUTPUTS)))
+        out = _ptrs(CPileupOut, (getattr(p, n) for n in PILEUP_OUTPUTS))
         st = CPileupStat()
         torch.cuda.synchronize(torch.device("cuda", self.gen.device))     # (the zero fills or the caller's own work on the sums, before another stream adds to them)
         self.gen._chk(self.gen.L.sqg_batch_pileup(self.gen.ctx, self.handle, C.byref(p.cfg), C.byref(org) if org is not None else None,
@@ -894,12 +896,8 @@ class SignalGenerator:
         split: any of "strand", "meth": a plane each; segs (by="kmer"): the segments counted, e.g. (3,) (default: the insert);
         [lo, hi): the key window, default the whole loaded genome / all rows.  outputs: the names wanted (default all); the others are None."""
         import torch
-        if not hasattr(self.L, "sqg_batch_pileup"):
-            raise SqgError(-1, "pileup", "this backend has no sqg_batch_pileup (include/sqg_pileup.h)")
-        bv = {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}.get(by, by)
-        nm = {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA}.get(norm, norm)
-        if not isinstance(bv, int) or not isinstance(nm, int):
-            raise SqgError(-1, "pileup", f"unknown by / norm {by!r} / {norm!r}")
+        _need(self.L, "sqg_batch_pileup", "sqg_pileup.h", "pileup")
+        bv, nm = _enum("pileup", by=by, norm=norm)
         sp = 0
         for name in ((split,) if isinstance(split, (str, int)) else split):
             bit = {"strand": PILEUP_SPLIT_STRAND, "meth": PILEUP_SPLIT_METH}.get(name, name)
@@ -909,9 +907,7 @@ class SignalGenerator:
         sg = 0
         for q in (() if segs is None else segs):
             sg |= 1 << int(q)
-        want = set(PILEUP_OUTPUTS if outputs is None else outputs)
-        if want - set(PILEUP_OUTPUTS):
-            raise SqgError(-1, "pileup", f"unknown outputs {sorted(want - set(PILEUP_OUTPUTS))}")
+        want = _want(outputs, PILEUP_OUTPUTS, "pileup")
         if lo is None:
             lo = 0
         if hi is None:
@@ -924,7 +920,7 @@ class SignalGenerator:
         if hi < lo:
             raise SqgError(-1, "pileup", "hi must not be below lo")
         planes = (2 if sp & PILEUP_SPLIT_STRAND else 1) * (2 if sp & PILEUP_SPLIT_METH else 1)
-        cfg = CPileupCfg(bv & 0xffffffff, sp & 0xffffffff, nm & 0xffffffff, int(trim), sg & 0xffffffff, int(lo), int(hi))
+        cfg = CPileupCfg(bv, sp & 0xffffffff, nm, int(trim), sg & 0xffffffff, int(lo), int(hi))
         dev = torch.device("cuda", self.device)
         return Pileup(cfg, planes, **{n: (torch.zeros((planes, hi - lo), dtype=torch.int32 if n == "n" else torch.int64, device=dev) if n in want else None)
                                       for n in PILEUP_OUTPUTS})

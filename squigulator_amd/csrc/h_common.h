@@ -76,49 +76,59 @@ struct HostPool {
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// device scratch of sqg_batch_chunks and sqg_batch_chunk_targets, grown by ensure(); the calls of a context share it (they block)
+struct sqg_ctx;
+static int ensure(sqg_ctx* c, void** p, size_t* cap, size_t need, size_t elem);      // (below)
+
+// A device array of a consumer call's scratch, grown by need() (ensure(): with slack, so that batches of similar size never re-allocate) and
+// freed when it goes or is assigned a fresh one: a scratch struct lists no pointer to free, `X = XScratch()` drops every array it holds.
+template <class T> struct DevBuf {
+    T* p = nullptr; size_t cap = 0;
+    DevBuf() = default; DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(DevBuf&& o) { drop(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; return *this; }
+    ~DevBuf() { drop(); }
+    int need(sqg_ctx* c, size_t n) { return ensure(c, (void**)&p, &cap, n, sizeof(T)); }
+    void drop() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// device scratch of sqg_batch_chunks and sqg_batch_chunk_targets; the calls of a context share it (they block)
 struct ChunkScratch {
-    long long* d_off = nullptr; size_t off_cap = 0; std::vector<long long> h_off;   // [n_reads+1] first chunk of every read, device and host
-    float2* d_const = nullptr; size_t const_cap = 0;           // [n_reads] {median, 1 / (1.4826 MAD)}
-    int* d_read = nullptr; size_t read_cap = 0;                // [n_chunks] chunk -> read
-    int2* d_ev = nullptr; size_t ev_cap = 0;                   // [n_chunks] every chunk's event range (k_chunk_labels)
-    unsigned int* d_wide = nullptr; size_t wide_cap = 0;       // the list of reads whose codes span more than the LDS histogram
-    unsigned int* d_ghist = nullptr; size_t ghist_cap = 0;     // the global histograms of the generic statistics paths
-    uint32_t* d_start = nullptr; size_t start_cap = 0;         // [n_events] first sample of every event within its read (k_target_scan)
-    long long* d_span = nullptr; size_t span_cap = 0; std::vector<long long> h_span;   // [2][n_reads] the inserts' spans of the slab, lo then hi (k_segments)
-    ChunkView* d_view = nullptr; size_t view_cap = 0;          // [n_reads] their events and bases
+    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first chunk of every read, device and host
+    DevBuf<float2> d_const;                                    // [n_reads] {median, 1 / (1.4826 MAD)}
+    DevBuf<int> d_read;                                        // [n_chunks] chunk -> read
+    DevBuf<int2> d_ev;                                         // [n_chunks] every chunk's event range (k_chunk_labels)
+    DevBuf<unsigned int> d_wide;                               // the list of reads whose codes span more than the LDS histogram
+    DevBuf<unsigned int> d_ghist;                              // the global histograms of the generic statistics paths
+    DevBuf<uint32_t> d_start;                                  // [n_events] first sample of every event within its read (k_target_scan)
+    DevBuf<long long> d_span; std::vector<long long> h_span;   // [2][n_reads] the inserts' spans of the slab, lo then hi (k_segments)
+    DevBuf<ChunkView> d_view;                                  // [n_reads] their events and bases
     const void* span_of = nullptr; unsigned long long span_run = 0;   // the batch (and its run index) spans and views were last made for
-    void release() { for (void* p : {(void*)d_off, (void*)d_const, (void*)d_read, (void*)d_ev, (void*)d_wide, (void*)d_ghist, (void*)d_start, (void*)d_span, (void*)d_view}) (void)hipFree(p);
-                     *this = ChunkScratch(); }
+    void release() { *this = ChunkScratch(); }
 };
 
-// device scratch of sqg_site_plan and sqg_batch_sites (h_sites.h), grown by ensure(): the plan and the per-site records
+// device scratch of sqg_site_plan and sqg_batch_sites (h_sites.h): the plan and the per-site records
 struct SiteScratch {
-    int* d_count = nullptr; size_t count_cap = 0; std::vector<int> h_count;        // [n_reads] sites of every read (k_site_scan<0>)
-    long long* d_off = nullptr; size_t off_cap = 0; std::vector<long long> h_off;   // [n_reads+1] first site of every read, device and host
-    SiteRec* d_rec = nullptr; size_t rec_cap = 0;              // [n_sites] (k_site_scan<1> -> k_site_emit)
-    uint8_t* d_skip = nullptr; size_t skip_cap = 0;            // [n_reads] the batch's reads shorter than a k-mer
+    DevBuf<int> d_count; std::vector<int> h_count;             // [n_reads] sites of every read (k_site_scan<0>)
+    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first site of every read, device and host
+    DevBuf<SiteRec> d_rec;                                     // [n_sites] (k_site_scan<1> -> k_site_emit)
+    DevBuf<uint8_t> d_skip;                                    // [n_reads] the batch's reads shorter than a k-mer
     const void* plan_of = nullptr; unsigned long long plan_run = 0; int plan_key[3] = {0, 0, 0};   // the batch (and its run index) and the win_len / before / focus the plan was last made for
-    void release() { for (void* p : {(void*)d_count, (void*)d_off, (void*)d_rec, (void*)d_skip}) (void)hipFree(p);
-                     *this = SiteScratch(); }
+    void release() { *this = SiteScratch(); }
 };
 
-// device scratch of sqg_batch_events (h_events_table.h), grown by ensure(): what the reduce pass needs of columns the caller did not ask for
+// device scratch of sqg_batch_events (h_events_table.h): what the reduce pass needs of columns the caller did not ask for
 struct EventScratch {
-    long long* d_start = nullptr; size_t start_cap = 0;        // [n_events] first stored sample of every event within its read (k_evtab_scan)
-    int* d_read = nullptr; size_t read_cap = 0;                // [n_events] event -> read
-    void release() { for (void* p : {(void*)d_start, (void*)d_read}) (void)hipFree(p);
-                     *this = EventScratch(); }
+    DevBuf<long long> d_start;                                 // [n_events] first stored sample of every event within its read (k_evtab_scan)
+    DevBuf<int> d_read;                                        // [n_events] event -> read
+    void release() { *this = EventScratch(); }
 };
 
-// device scratch of sqg_batch_pileup (h_pileup.h), grown by ensure(): the scan pass's columns the key or a split needs, the reads' origins, the counters
+// device scratch of sqg_batch_pileup (h_pileup.h): the scan pass's columns the key or a split needs, the reads' origins, the counters
 struct PileupScratch {
-    uint32_t* d_kmer = nullptr; size_t kmer_cap = 0;           // [n_events] pore-table row of every event (k_evtab_scan)
-    uint8_t* d_seg = nullptr; size_t seg_cap = 0;              // [n_events] its segment
-    PileRead* d_pr = nullptr; size_t pr_cap = 0; std::vector<PileRead> h_pr;   // [n_reads] origin and insert of every read, device and host
-    unsigned long long* d_stat = nullptr; size_t stat_cap = 0;   // {counted, outside}
-    void release() { for (void* p : {(void*)d_kmer, (void*)d_seg, (void*)d_pr, (void*)d_stat}) (void)hipFree(p);
-                     *this = PileupScratch(); }
+    DevBuf<uint32_t> d_kmer;                                   // [n_events] pore-table row of every event (k_evtab_scan)
+    DevBuf<uint8_t> d_seg;                                     // [n_events] its segment
+    DevBuf<PileRead> d_pr; std::vector<PileRead> h_pr;         // [n_reads] origin and insert of every read, device and host
+    DevBuf<unsigned long long> d_stat;                         // {counted, outside}
+    void release() { *this = PileupScratch(); }
 };
 
 struct sqg_ctx {

@@ -15,27 +15,21 @@ static int segments_run(sqg_ctx* c, sqg_batch* b, long long* seg, long long* shi
     ChunkScratch& X = c->chunk;
     const size_t n = (size_t)b->n;
     int rc;
-    if ((rc = ensure(c, (void**)&X.d_span, &X.span_cap, 2 * n, sizeof(long long)))) return rc;
-    if ((rc = ensure(c, (void**)&X.d_view, &X.view_cap, n, sizeof(ChunkView)))) return rc;
+    if ((rc = X.d_span.need(c, 2 * n)) || (rc = X.d_view.need(c, n))) return rc;
     X.h_span.resize(2 * n);
     X.span_of = nullptr;                                                // (until the new spans are there)
-    const bool prefix = (c->cfg.flags & SQG_PREFIX) != 0, rna = (c->cfg.flags & SQG_RNA) != 0;
     SegParams Q{};
-    Q.reads = (const ReadDesc*)b->d_reads; Q.sig_off = c->slot[b->slot].d_sigoff;
-    Q.dwell = c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr;
-    Q.const_sps = std::max((int)c->cfg.profile.dwell_mean, 1);
-    Q.n_reads = b->n; Q.kind = !prefix ? SEG_NONE : rna ? SEG_RNA : SEG_DNA;
-    if (Q.kind == SEG_DNA) { Q.p0 = (int)strlen(kStallDna); Q.p1 = Q.p0 + (int)strlen(kAdaptorDna); }
-    if (Q.kind == SEG_RNA) {
+    Q.bv = batch_view(c, b);
+    if (Q.bv.kind == SEG_RNA) {
         // development build: SQG_TEST_SEG_SPS=N makes the window 79 N samples long here (not in the generator), so that it reaches into
         // the inserts and k_target_shift has samples to lower
-        const int sps = dev_env_int(SQG_DEV_ENV("SQG_TEST_SEG_SPS"), (int)c->cfg.profile.dwell_mean);
-        Q.p0 = kPolyA; Q.p1 = kPolyA + (int)strlen(kAdaptorRna); Q.shift_len = (long long)strlen(kAdaptorRna) * sps;
+        const int sps = dev_env_int(SQG_DEV_ENV("SQG_TEST_SEG_SPS"), Q.bv.const_sps);
+        Q.shift_len = (long long)(Q.bv.p1 - Q.bv.p0) * sps;             // (the adaptor's bases)
     }
-    Q.seg = seg; Q.shift = shift; Q.lo = X.d_span; Q.hi = X.d_span + n; Q.view = X.d_view;
+    Q.seg = seg; Q.shift = shift; Q.lo = X.d_span.p; Q.hi = X.d_span.p + n; Q.view = X.d_view.p;
     hipLaunchKernelGGL(k_segments, dim3((unsigned)n), dim3(64), 0, c->stream, Q);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(X.h_span.data(), X.d_span, 2 * n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(X.h_span.data(), X.d_span.p, 2 * n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     X.span_of = b; X.span_run = b->run_idx;
     return SQG_OK;
@@ -43,10 +37,9 @@ static int segments_run(sqg_ctx* c, sqg_batch* b, long long* seg, long long* shi
 
 extern "C" int sqg_batch_segments(sqg_ctx_t* c, sqg_batch_t* b, const sqg_segments_t* out) {
     static const char who[] = "sqg_batch_segments";
-    if (!c) return SQG_EINVAL;
-    if (!b || !out) { c->err = std::string(who) + ": batch and out must not be NULL"; return SQG_EINVAL; }
-    if (!b->ran) { c->err = std::string(who) + ": the batch has not been run"; return SQG_ESEQUENCE; }
-    if (int rc = chunk_owned(c, b, who, c->use_dwell_stream)) return rc;
+    int rc = check_open(c, b, out, "out", who);
+    if (rc || (rc = Check{c, who}.ran(b))) return rc;
+    if ((rc = chunk_owned(c, b, who, c->use_dwell_stream))) return rc;
     if (b->n == 0 || !(out->seg || out->shift)) return SQG_OK;
     return segments_run(c, b, (long long*)out->seg, (long long*)out->shift);
 }
@@ -55,7 +48,7 @@ extern "C" int sqg_chunk_plan_trimmed(sqg_ctx_t* c, sqg_batch_t* b, const sqg_ch
     static const char who[] = "sqg_chunk_plan_trimmed";
     int rc = chunk_check(c, b, cfg, who, true);
     if (rc) return rc;
-    if (!n_chunks) { c->err = std::string(who) + ": n_chunks must not be NULL"; return SQG_EINVAL; }
+    if ((rc = Check{c, who}.null(n_chunks, "n_chunks"))) return rc;
     ChunkJob J;
     if ((rc = chunk_begin(c, b, cfg, who, c->use_dwell_stream, &J, true))) return rc;
     if (chunk_off) { chunk_off[0] = 0; for (int i = 0; i < b->n; i++) chunk_off[i + 1] = (int64_t)J.plan[i + 1]; }

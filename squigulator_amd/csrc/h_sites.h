@@ -1,35 +1,29 @@
 // h_sites.h -- sqg_site_plan, sqg_batch_sites: CpG-centred signal windows of a batch with their methylation labels, left on the device
-// Host side of include/sqg_sites.h; included by sqg_hip.hip behind h_segments.h.  The lifetime rule, the job and the statistics pass are h_chunks.h's.
+// Host side of include/sqg_sites.h; included by sqg_hip.hip behind h_segments.h.  The opening of the checks, the batch's view, the lifetime rule and the statistics job are h_chunks.h's.
 #pragma once
 
 static int site_check(sqg_ctx* c, sqg_batch* b, const sqg_site_cfg_t* cfg, const char* who) {
-    if (!c) return SQG_EINVAL;
-    auto bad = [&](const char* what) { c->err = std::string(who) + ": " + what; return SQG_EINVAL; };
-    if (!b || !cfg) return bad("batch and cfg must not be NULL");
-    if (c->cfg.flags & SQG_RNA) return bad("sites: not with SQG_RNA");
-    if (c->cfg.flags & SQG_PREFIX) return bad("sites: not with SQG_PREFIX");
-    if (cfg->win_len < 16 || cfg->win_len > 65536 || (cfg->win_len & 7)) return bad("win_len must be a multiple of 8 in 16 .. 65536");
-    if (cfg->before < 0 || cfg->before >= cfg->win_len) return bad("before must be in 0 .. win_len - 1");
-    if (cfg->focus < 0 || cfg->focus >= c->k) return bad("focus must be in 0 .. k - 1");
-    if (cfg->ctx_len < 0 || cfg->ctx_len > 255) return bad("ctx_len must be in 0 .. 255");
-    if (cfg->ctx_before < 0 || cfg->ctx_before > std::max(cfg->ctx_len - 1, 0)) return bad("ctx_before must be in 0 .. ctx_len - 1 (0 when ctx_len is 0)");
-    if (cfg->dtype != SQG_CHUNK_F16 && cfg->dtype != SQG_CHUNK_F32) return bad("unknown dtype");
-    if (cfg->norm != SQG_CHUNK_MEDMAD && cfg->norm != SQG_CHUNK_PA) return bad("unknown norm");
-    if (!b->ran) { c->err = std::string(who) + ": the batch has not been run"; return SQG_ESEQUENCE; }
-    return SQG_OK;
+    if (int rc = check_open(c, b, cfg, "cfg", who)) return rc;
+    const Check K{c, who};
+    if (c->cfg.flags & SQG_RNA) return K.bad("sites: not with SQG_RNA");
+    if (c->cfg.flags & SQG_PREFIX) return K.bad("sites: not with SQG_PREFIX");
+    if (cfg->win_len < 16 || cfg->win_len > 65536 || (cfg->win_len & 7)) return K.bad("win_len must be a multiple of 8 in 16 .. 65536");
+    if (cfg->before < 0 || cfg->before >= cfg->win_len) return K.bad("before must be in 0 .. win_len - 1");
+    if (cfg->focus < 0 || cfg->focus >= c->k) return K.bad("focus must be in 0 .. k - 1");
+    if (cfg->ctx_len < 0 || cfg->ctx_len > 255) return K.bad("ctx_len must be in 0 .. 255");
+    if (cfg->ctx_before < 0 || cfg->ctx_before > std::max(cfg->ctx_len - 1, 0)) return K.bad("ctx_before must be in 0 .. ctx_len - 1 (0 when ctx_len is 0)");
+    if (!dtype_ok(cfg->dtype)) return K.bad("unknown dtype");
+    if (!norm_ok(cfg->norm)) return K.bad("unknown norm");
+    return K.ran(b);
 }
 
 // what both kernels take, all but the caller's outputs, for a batch that owns its device results and dwells
 static SiteParams site_params(sqg_ctx* c, sqg_batch* b, const sqg_site_cfg_t* cfg) {
     SiteParams Q{};
-    Q.reads = (const ReadDesc*)b->d_reads; Q.bases = (const uint8_t*)b->d_bases;
-    Q.dwell = c->use_dwell_stream ? (const uint16_t*)c->cset[b->cset].d_dwell : (const uint16_t*)nullptr;
-    Q.sig_off = c->slot[b->slot].d_sigoff; Q.sig = c->slot[b->slot].d_sig;
-    Q.skip = b->short_read.empty() ? nullptr : c->site.d_skip;
-    Q.const_sps = (int)c->cfg.profile.dwell_mean; Q.meth = (c->cfg.flags & SQG_METH) ? 1 : 0; Q.n_reads = b->n;
+    Q.bv = batch_view(c, b);
+    Q.skip = b->short_read.empty() ? nullptr : c->site.d_skip.p;
     Q.L = cfg->win_len; Q.before = cfg->before; Q.focus = cfg->focus; Q.B = cfg->ctx_len; Q.cb = cfg->ctx_before;
-    Q.count = c->site.d_count; Q.site_off = c->site.d_off; Q.rec = c->site.d_rec;
-    Q.range = c->cfg.profile.range; Q.dig = c->cfg.profile.digitisation;
+    Q.count = c->site.d_count.p; Q.site_off = c->site.d_off.p; Q.rec = c->site.d_rec.p;
     return Q;
 }
 
@@ -43,22 +37,21 @@ static int site_plan_run(sqg_ctx* c, sqg_batch* b, const sqg_site_cfg_t* cfg) {
         X.plan_key[0] == cfg->win_len && X.plan_key[1] == cfg->before && X.plan_key[2] == cfg->focus) return SQG_OK;
     X.plan_of = nullptr;                                                // (until the new plan is there)
     int rc;
-    if ((rc = ensure(c, (void**)&X.d_count, &X.count_cap, n, sizeof(int)))) return rc;
-    if ((rc = ensure(c, (void**)&X.d_off, &X.off_cap, n + 1, sizeof(long long)))) return rc;
+    if ((rc = X.d_count.need(c, n)) || (rc = X.d_off.need(c, n + 1))) return rc;
     const hipStream_t st = c->stream;
     if (!b->short_read.empty()) {
-        if ((rc = ensure(c, (void**)&X.d_skip, &X.skip_cap, n, sizeof(uint8_t)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(X.d_skip, b->short_read.data(), n, hipMemcpyHostToDevice, st));
+        if ((rc = X.d_skip.need(c, n))) return rc;
+        HIPCHK(c, hipMemcpyAsync(X.d_skip.p, b->short_read.data(), n, hipMemcpyHostToDevice, st));
     }
     X.h_count.resize(n); X.h_off.resize(n + 1);
     const SiteParams Q = site_params(c, b, cfg);
     hipLaunchKernelGGL(k_site_scan<0>, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(X.h_count.data(), X.d_count, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(X.h_count.data(), X.d_count.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     X.h_off[0] = 0;
     for (size_t i = 0; i < n; i++) X.h_off[i + 1] = X.h_off[i] + X.h_count[i];
-    HIPCHK(c, hipMemcpyAsync(X.d_off, X.h_off.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(X.d_off.p, X.h_off.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));                                // (h_off is the scratch's: the copy has left it before anybody rewrites it)
     X.plan_of = b; X.plan_run = b->run_idx;
     X.plan_key[0] = cfg->win_len; X.plan_key[1] = cfg->before; X.plan_key[2] = cfg->focus;
@@ -69,7 +62,7 @@ extern "C" int sqg_site_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_t*
     static const char who[] = "sqg_site_plan";
     int rc = site_check(c, b, cfg, who);
     if (rc) return rc;
-    if (!n_sites) { c->err = std::string(who) + ": n_sites must not be NULL"; return SQG_EINVAL; }
+    if ((rc = Check{c, who}.null(n_sites, "n_sites"))) return rc;
     if ((rc = chunk_owned(c, b, who, c->use_dwell_stream))) return rc;
     if (b->n == 0) { if (site_off) site_off[0] = 0; *n_sites = 0; return SQG_OK; }
     if ((rc = site_plan_run(c, b, cfg))) return rc;
@@ -82,27 +75,20 @@ extern "C" int sqg_batch_sites(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_
     static const char who[] = "sqg_batch_sites";
     int rc = site_check(c, b, cfg, who);
     if (rc) return rc;
-    if (!out) { c->err = std::string(who) + ": out must not be NULL"; return SQG_EINVAL; }
-    if (out->signal && ((uintptr_t)out->signal & 15)) { c->err = std::string(who) + ": signal must be 16-byte aligned"; return SQG_EINVAL; }
-    // the chunk job of the whole reads, one chunk of win_len samples each at the most: its spans, parameters and scratch are what the
-    // statistics pass takes
-    sqg_chunk_cfg_t cf{};
-    cf.chunk_len = cfg->win_len; cf.stride = INT32_MAX; cf.max_label = 0; cf.dtype = cfg->dtype; cf.norm = cfg->norm;
-    ChunkJob J;
-    if ((rc = chunk_begin(c, b, &cf, who, c->use_dwell_stream, &J)) || J.P.n_reads == 0) return rc;
+    const Check K{c, who};
+    if ((rc = K.null(out, "out"))) return rc;
+    if (out->signal && ((uintptr_t)out->signal & 15)) return K.bad("signal must be 16-byte aligned");
+    ChunkJob J;                                                         // the statistics job of the whole reads
+    if ((rc = spans_open(c, b, who, c->use_dwell_stream, false, &J)) || J.P.bv.n_reads == 0) return rc;
     if ((rc = site_plan_run(c, b, cfg))) return rc;
     const int n = b->n;
     const long long n_sites = c->site.h_off[(size_t)n];
     const hipStream_t st = J.st;
     const bool want_rows = n_sites > 0 && (out->signal || out->context || out->ctx_start);
     const bool want_stats = out->med2 || out->mad4 || (out->signal && n_sites > 0 && cfg->norm == SQG_CHUNK_MEDMAD);
-    if (want_stats) {
-        if ((rc = chunk_upload(c, &J))) return rc;
-        J.P.med2 = out->med2; J.P.mad4 = out->mad4;
-        if ((rc = chunk_stats_run(c, b, J))) return rc;
-    }
+    if (want_stats && (rc = stats_run(c, b, J, out->med2, out->mad4))) return rc;
     if (n_sites > 0) {
-        if ((rc = ensure(c, (void**)&c->site.d_rec, &c->site.rec_cap, (size_t)n_sites, sizeof(SiteRec)))) return rc;
+        if ((rc = c->site.d_rec.need(c, (size_t)n_sites))) return rc;
         SiteParams Q = site_params(c, b, cfg);
         Q.n_sites = n_sites; Q.consts = J.P.consts;
         Q.label = out->label; Q.site_read = out->site_read; Q.site_pos = out->site_pos; Q.win_start = (long long*)out->win_start;
@@ -112,11 +98,9 @@ extern "C" int sqg_batch_sites(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_
         if (want_rows) {
             const int per = CHUNK_WG / 64;
             const unsigned wgs = (unsigned)std::min<long long>((n_sites + per - 1) / per, 1LL << 20);
-            const bool f32 = cfg->dtype == SQG_CHUNK_F32, pa = cfg->norm == SQG_CHUNK_PA;
-#define SITE_EMIT(F, A) hipLaunchKernelGGL((k_site_emit<F, A>), dim3(wgs), dim3(CHUNK_WG), 0, st, Q)
-            if (f32) { if (pa) SITE_EMIT(true, true); else SITE_EMIT(true, false); }
-            else { if (pa) SITE_EMIT(false, true); else SITE_EMIT(false, false); }
-#undef SITE_EMIT
+            dispatch(cfg->dtype == SQG_CHUNK_F32, cfg->norm == SQG_CHUNK_PA, [&](auto F, auto A) {
+                hipLaunchKernelGGL((k_site_emit<decltype(F)::value, decltype(A)::value>), dim3(wgs), dim3(CHUNK_WG), 0, st, Q);
+            });
         }
         HIPCHK(c, hipGetLastError());
         if ((rc = dbg_sync(c, "k_site_emit"))) return rc;

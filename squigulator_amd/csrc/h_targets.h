@@ -1,5 +1,5 @@
 // h_targets.h -- sqg_batch_chunk_targets: clean signal, moves and k-mer rows for the chunks of a batch, left on the device
-// Host side of include/sqg_targets.h; included by sqg_hip.hip behind h_chunks.h, whose checks, plan and statistics pass it uses.
+// Host side of include/sqg_targets.h; included by sqg_hip.hip behind h_chunks.h, whose checks, job (the batch's view, the plan) and statistics pass it uses.
 #pragma once
 
 // sqg_batch_chunk_targets, and sqg_batch_chunk_targets_trimmed (h_segments.h) with trimmed
@@ -8,11 +8,11 @@ static int targets_run(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, con
     if (cfg) { cf = *cfg; cf.max_label = 0; }                            // (ignored here)
     int rc = chunk_check(c, b, cfg ? &cf : nullptr, who, trimmed);
     if (rc) return rc;
-    auto bad = [&](const char* what) { c->err = std::string(who) + ": " + what; return SQG_EINVAL; };
-    if (!tg) return bad("tg must not be NULL");
-    if (((uintptr_t)tg->clean & 15) || ((uintptr_t)tg->clean_raw & 15) || ((uintptr_t)tg->kmer & 15)) return bad("clean, clean_raw and kmer must be 16-byte aligned");
-    if ((uintptr_t)tg->moves & 7) return bad("moves must be 8-byte aligned");
-    if (!tg->med2 != !tg->mad4) return bad("med2 and mad4: both or neither");
+    const Check K{c, who};
+    if ((rc = K.null(tg, "tg"))) return rc;
+    if (((uintptr_t)tg->clean & 15) || ((uintptr_t)tg->clean_raw & 15) || ((uintptr_t)tg->kmer & 15)) return K.bad("clean, clean_raw and kmer must be 16-byte aligned");
+    if ((uintptr_t)tg->moves & 7) return K.bad("moves must be 8-byte aligned");
+    if (!tg->med2 != !tg->mad4) return K.bad("med2 and mad4: both or neither");
     // (stricter than every output set needs -- only the statistics read the signal slab, a constant-dwell context reads no dwells -- but
     // one rule for the call, the one sqg_batch_chunks has: the batch owns its device results and its dwell set, or nothing is written)
     ChunkJob J;
@@ -26,23 +26,18 @@ static int targets_run(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, con
             return SQG_EOVERFLOW;
         }
     if ((rc = chunk_upload(c, &J))) return rc;
-    if (c->use_dwell_stream && (rc = ensure(c, (void**)&c->chunk.d_start, &c->chunk.start_cap, (size_t)std::max<long long>(b->n_events, 1), sizeof(uint32_t)))) return rc;
+    if (c->use_dwell_stream && (rc = c->chunk.d_start.need(c, (size_t)std::max<long long>(b->n_events, 1)))) return rc;
     const ChunkParams& P = J.P;
     const hipStream_t st = J.st;
-    const ReadDesc* reads = (const ReadDesc*)b->d_reads;
     const bool want_consts = tg->clean && cf.norm == SQG_CHUNK_MEDMAD;
-    if (want_consts && !tg->med2) { if ((rc = chunk_stats_run(c, b, J))) return rc; }
+    if (want_consts && !tg->med2) { if ((rc = stats_run(c, b, J, nullptr, nullptr))) return rc; }
     else if (want_consts) hipLaunchKernelGGL(k_chunk_consts, dim3((unsigned)((n + CHUNK_WG - 1) / CHUNK_WG)), dim3(CHUNK_WG), 0, st, P, (const int*)tg->med2, (const int*)tg->mad4);
     hipLaunchKernelGGL(k_chunk_index, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P);
     // pass A: the event starts
     if (c->use_dwell_stream)
-        hipLaunchKernelGGL(k_target_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P, reads, (const uint16_t*)c->cset[b->cset].d_dwell, c->chunk.d_start);
+        hipLaunchKernelGGL(k_target_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, P, c->chunk.d_start.p);
     // pass B: the rows
-    TargetParams T{};
-    T.reads = reads; T.bases = (const uint8_t*)b->d_bases; T.model = c->d_model;
-    T.ev_start = c->use_dwell_stream ? c->chunk.d_start : nullptr;
-    T.k = c->k; T.meth = (c->cfg.flags & SQG_METH) ? 1 : 0; T.rna = (c->cfg.flags & SQG_RNA) ? 1 : 0; T.const_sps = std::max((int)c->cfg.profile.dwell_mean, 1);
-    T.clean = tg->clean; T.clean_raw = tg->clean_raw; T.moves = tg->moves; T.kmer = tg->kmer;
+    const TargetParams T{c->use_dwell_stream ? c->chunk.d_start.p : nullptr, tg->clean, tg->clean_raw, tg->moves, tg->kmer};
     const TargetGeom geom = tgt_geom(P.L);
     const unsigned wgs = (unsigned)std::min<long long>((n_chunks * geom.n_tiles + geom.cpb - 1) / geom.cpb, 1LL << 20);
     const int clean = !tg->clean ? 0 : 1 + (cf.dtype == SQG_CHUNK_F32 ? 2 : 0) + (cf.norm == SQG_CHUNK_PA ? 1 : 0);
@@ -55,7 +50,7 @@ static int targets_run(sqg_ctx* c, sqg_batch* b, const sqg_chunk_cfg_t* cfg, con
 #undef TGT_CASE
     }
     // the RNA adaptor's level-shift window, where it reaches into an insert (include/sqg_segments.h)
-    if (trimmed && T.rna && (c->cfg.flags & SQG_PREFIX) && (tg->clean || tg->clean_raw))
+    if (trimmed && P.bv.rna && (c->cfg.flags & SQG_PREFIX) && (tg->clean || tg->clean_raw))
         hipLaunchKernelGGL(k_target_shift, dim3((unsigned)std::min<long long>(n_chunks, 4096)), dim3(64), 0, st, P, T, clean, segments_shift_code(c));
     HIPCHK(c, hipGetLastError());
     if ((rc = dbg_sync(c, "k_target_emit"))) return rc;

@@ -8,9 +8,10 @@
 //   k_chunk_hist_long, k_chunk_select_long   one long read over many workgroups: global histogram, then the selection by one workgroup
 //   k_chunk_consts       the same constants from med2 / mad4 the caller passed in (sqg_batch_chunk_targets with the statistics of an earlier call)
 //   k_chunk_index        chunk -> read, chunk -> first sample
-//   k_chunk_emit         streaming: 2 B/sample in, the chunk rows out in 16-byte stores
+//   k_chunk_emit         streaming: 2 B/sample in, the chunk rows out in 16-byte stores (chunk_row8, which k_sites.h's rows go through too)
 //   k_chunk_labels       one workgroup per read: one scan of its dwells finds every chunk's event range [e0, e1); then the codes
 // Which statistics path a read took shows in no output: all three count the same integers.
+// BatchView, defined here, is what these and the kernels of k_targets.h, k_segments.h, k_sites.h, k_events_table.h and k_pileup.h take of the batch.
 #pragma once
 
 #define CHUNK_WG 256
@@ -29,24 +30,42 @@ struct ChunkView {
     int pad;                         // (to the struct's 8-byte alignment: written, so that the scratch holds no stale bytes)
 };
 
-struct ChunkParams {
+// What every kernel that reads a finished batch takes of it (h_chunks.h: batch_view): the batch's descriptors, bases, dwells and signal,
+// the pore table, and the context's settings.  The callers' parameter structs embed it and add what is their own.
+#define SEG_NONE 0                   // no SQG_PREFIX: the whole read is insert
+#define SEG_DNA 1                    // stall + adaptor + read, stored order = generation order
+#define SEG_RNA 2                    // read + poly-A + adaptor, then the stall chain; stored reversed
+struct BatchView {
+    const ReadDesc* reads;           // [n_reads]
+    const uint8_t* bases;
+    const float2* model;             // {level_mean, -}
+    const uint16_t* dwell;           // the batch's dwells; null: a constant-dwell context, every dwell is const_sps
+    const long long* sig_off;        // [n_reads+1]
     const int16_t* sig;              // the batch's signal slab
+    int const_sps, k, meth, rna, n_reads;   // rna: the signal is stored reversed
+    int kind;                        // SEG_NONE / SEG_DNA / SEG_RNA
+    int p0, p1;                      // SEG_DNA: events of the stall, of stall + adaptor.  SEG_RNA: bases of the poly-A, of poly-A + adaptor
+    double range, dig;               // the profile's range and digitisation
+};
+
+struct ChunkParams {
+    BatchView bv;
     const long long* lo;             // [n_reads] every read's span of the slab, [lo, hi): the batch's sig_off and sig_off + 1, or the
     const long long* hi;             //           spans k_segments wrote
     const ChunkView* view;           // [n_reads] the spans' events and bases; null: the whole read (ReadDesc's ev_off, base_off, ne0)
-    const long long* chunk_off;      // [n_reads+1] first chunk of every read
-    int n_reads;
-    long long n_chunks;
-    int L, S, W;
+    // the statistics pass (a job of spans alone: h_chunks.h, spans_open / stats_run)
     int hist_max;                    // bins the LDS path may use (CHUNK_HIST; 0: every read takes the wide path)
     long long one_wg_max;            // samples up to which one workgroup takes a read (beyond: the long path, launched per read by the host)
     float2* consts;                  // [n_reads] {median, 1 / (1.4826 * MAD)} as the emit kernel uses them
     int* med2; int* mad4;            // [n_reads] outputs, may be null
     unsigned int* wide_list;         // [0] reads listed, [1 + i] their indices
     unsigned int* ghist;             // [CHUNK_WIDE_SLOTS][2][CHUNK_GBINS]
+    // the chunk calls' plan on top of it
+    const long long* chunk_off;      // [n_reads+1] first chunk of every read
+    long long n_chunks;
+    int L, S, W;
     int* chunk_read;                 // [n_chunks] (the caller's array or scratch)
     int* chunk_read_out; long long* chunk_start_out;   // outputs, may be null
-    double range, dig;               // PA: the profile's range and digitisation
 };
 
 // exclusive scan of one value per thread over the workgroup (CHUNK_WG threads); sh: 8 words of LDS; *total <- the sum
@@ -117,7 +136,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats(ChunkParams P) {
     const long long o = P.lo[r], n = P.hi[r] - o;
     if (n <= 0) { if (t == 0) chunk_write_stats(P, r, 0, 0); return; }
     if (n > P.one_wg_max) return;                           // the long path's
-    const int16_t* p = P.sig + o;
+    const int16_t* p = P.bv.sig + o;
     int mn = 32767, mx = -32768;
     chunk_for_samples(p, n, 0, 1, [&](int v) { mn = min(mn, v); mx = max(mx, v); });
 #pragma unroll
@@ -177,7 +196,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats_wide(ChunkParams P) {
         for (int i = threadIdx.x; i < 2 * CHUNK_GBINS; i += CHUNK_WG) __hip_atomic_store(&H[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __threadfence();
         __syncthreads();
-        chunk_for_samples(P.sig + o, n, 0, 1, [&](int v) { atomicAdd(&H[v + 32768], 1u); });
+        chunk_for_samples(P.bv.sig + o, n, 0, 1, [&](int v) { atomicAdd(&H[v + 32768], 1u); });
         __threadfence();
         __syncthreads();
         int med2, mad4;
@@ -191,7 +210,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_stats_wide(ChunkParams P) {
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_hist_long(ChunkParams P, int r) {
     const long long o = P.lo[r], n = P.hi[r] - o;
     unsigned int* H = P.ghist;
-    chunk_for_samples(P.sig + o, n, blockIdx.x, gridDim.x, [&](int v) { atomicAdd(&H[v + 32768], 1u); });
+    chunk_for_samples(P.bv.sig + o, n, blockIdx.x, gridDim.x, [&](int v) { atomicAdd(&H[v + 32768], 1u); });
 }
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_select_long(ChunkParams P, int r) {
     __shared__ unsigned long long sh[8];
@@ -203,7 +222,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_chunk_select_long(ChunkParams P, i
 
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_consts(ChunkParams P, const int* __restrict__ med2, const int* __restrict__ mad4) {
     const int r = blockIdx.x * CHUNK_WG + threadIdx.x;
-    if (r < P.n_reads) chunk_write_stats(P, r, med2[r], mad4[r]);              // (P.med2 / P.mad4 are null: only the constants are written)
+    if (r < P.bv.n_reads) chunk_write_stats(P, r, med2[r], mad4[r]);              // (P.med2 / P.mad4 are null: only the constants are written)
 }
 
 __global__ __launch_bounds__(CHUNK_WG) void k_chunk_index(ChunkParams P) {
@@ -245,38 +264,43 @@ __device__ static inline void chunk_store8(void* out, long long at, const float 
 struct ChunkEmitGeom { int g8, cpb; };
 __host__ __device__ static inline ChunkEmitGeom chunk_emit_geom(int L) { return {L >> 3, (L >> 3) >= CHUNK_WG ? 1 : CHUNK_WG / (L >> 3)}; }
 
-// A workgroup takes 256 / (L / 8) chunks at a time (one for L >= 2048); a thread 8 consecutive samples: 20 bytes in (the read starts at
-// any 2-byte address), 16 or 32 bytes out.  offset: the reads' slow5 offsets (PA), from the batch's descriptors.
+// 8 consecutive samples from any 2-byte address, normalised (PA: with the read's slow5 offset; else with cs), into a 16-byte-aligned row
+// at out[at ..]: the aligned 4-byte words that cover them, shifted when the address is odd -- 20 bytes in, no misaligned wide load is
+// issued; 16 or 32 bytes out.  k_chunk_emit and k_site_emit (k_sites.h).
 template <bool F32, bool PA>
-__global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, const ReadDesc* __restrict__ reads, void* __restrict__ out) {
+__device__ static inline void chunk_row8(const BatchView& V, const int16_t* src, float2 cs, double offset, void* out, long long at) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>((uintptr_t)src & ~(uintptr_t)3);
+    const bool odd = ((uintptr_t)src & 2) != 0;
+    uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
+    if (odd) {
+        const uint32_t a4 = q[4];
+        a0 = (a0 >> 16) | (a1 << 16); a1 = (a1 >> 16) | (a2 << 16); a2 = (a2 >> 16) | (a3 << 16); a3 = (a3 >> 16) | (a4 << 16);
+    }
+    const uint32_t a[4] = {a0, a1, a2, a3};
+    float x[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int raw = (int)(int16_t)((a[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+        x[i] = PA ? chunk_norm_pa(raw, offset, V.range, V.dig) : chunk_norm_medmad(raw, cs);
+    }
+    chunk_store8<F32>(out, at, x);
+}
+
+// A workgroup takes 256 / (L / 8) chunks at a time (one for L >= 2048); a thread 8 consecutive samples (chunk_row8).  PA takes the
+// reads' slow5 offsets from the batch's descriptors.
+template <bool F32, bool PA>
+__global__ __launch_bounds__(CHUNK_WG) void k_chunk_emit(ChunkParams P, void* __restrict__ out) {
     const auto [g8, cpb] = chunk_emit_geom(P.L);
     const int sub = (int)threadIdx.x / g8, w0 = (int)threadIdx.x - sub * g8;
     if (sub >= cpb) return;
     for (long long c = (long long)blockIdx.x * cpb + sub; c < P.n_chunks; c += (long long)gridDim.x * cpb) {
         const int r = P.chunk_read[c];
         const long long j = c - P.chunk_off[r];
-        const int16_t* src0 = P.sig + P.lo[r] + j * P.S;
+        const int16_t* src0 = P.bv.sig + P.lo[r] + j * P.S;
         const float2 cs = P.consts[r];
         double offset = 0.0;
-        if (PA) offset = reads[r].offset;
-        for (int w = w0; w < g8; w += CHUNK_WG) {
-            const int16_t* src = src0 + (long long)w * 8;
-            const uint32_t* q = reinterpret_cast<const uint32_t*>((uintptr_t)src & ~(uintptr_t)3);
-            const bool odd = ((uintptr_t)src & 2) != 0;
-            uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
-            if (odd) {
-                const uint32_t a4 = q[4];
-                a0 = (a0 >> 16) | (a1 << 16); a1 = (a1 >> 16) | (a2 << 16); a2 = (a2 >> 16) | (a3 << 16); a3 = (a3 >> 16) | (a4 << 16);
-            }
-            const uint32_t a[4] = {a0, a1, a2, a3};
-            float x[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int raw = (int)(int16_t)((a[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-                x[i] = PA ? chunk_norm_pa(raw, offset, P.range, P.dig) : chunk_norm_medmad(raw, cs);
-            }
-            chunk_store8<F32>(out, c * (long long)P.L + (long long)w * 8, x);
-        }
+        if (PA) offset = P.bv.reads[r].offset;
+        for (int w = w0; w < g8; w += CHUNK_WG) chunk_row8<F32, PA>(P.bv, src0 + (long long)w * 8, cs, offset, out, c * (long long)P.L + (long long)w * 8);
     }
 }
 
@@ -349,19 +373,20 @@ __device__ static inline void chunk_for_event_starts(const ChunkOrigin& og, cons
 
 // The chunk boundaries in (E[e], E[e] + dwell[e]] belong to event e + 1 (the first event that starts at or behind them), those at or before 0
 // to event 0, those behind the last start to n_events.
-__global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, const ReadDesc* __restrict__ reads, const uint8_t* __restrict__ bases,
-                                                           const uint16_t* __restrict__ dwell, int const_sps, int rna, int meth, int div64, int2* ev,
-                                                           uint8_t* labels, int* label_len) {
+__global__ __launch_bounds__(CHUNK_WG) void k_chunk_labels(ChunkParams P, int div64, int2* ev, uint8_t* labels, int* label_len) {
     __shared__ unsigned long long sh[8];
+    const BatchView& V = P.bv;
+    const uint8_t* __restrict__ bases = V.bases;
+    const int rna = V.rna, meth = V.meth;
     const int r = blockIdx.x, t = threadIdx.x;
     ChunkGeom G;
     G.c0 = P.chunk_off[r]; G.nc = P.chunk_off[r + 1] - G.c0;
     if (G.nc <= 0) return;
     G.n = P.hi[r] - P.lo[r]; G.L = P.L; G.S = P.S; G.rna = rna;
     G.small = !div64 && G.n < (1LL << 31);                  // div64: the development build's test hook, the 64-bit divisions on every read
-    const ChunkOrigin og = chunk_origin(P, reads[r], r);
+    const ChunkOrigin og = chunk_origin(P, V.reads[r], r);
     const int ne = og.ne;
-    chunk_for_event_starts(og, dwell, const_sps, sh, [&, ne](int e, long long E, int d) {
+    chunk_for_event_starts(og, V.dwell, V.const_sps, sh, [&, ne](int e, long long E, int d) {
         if (e == 0) chunk_mark(G, ev, -CHUNK_BIG, 0, 0);
         chunk_mark(G, ev, E, e == ne - 1 ? CHUNK_BIG : E + d, e + 1);
     });

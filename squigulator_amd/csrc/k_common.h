@@ -96,6 +96,11 @@ __device__ static inline int16_t to_i16(double v) {
     return (int16_t)(uint16_t)((uint32_t)t & 0xffffu);
 }
 
+// the noise-free code of pore-table row `rank` in a read with that offset (src/gensig.c:270): what the consumer kernels write as a level
+__device__ static inline int16_t level_code(const float2* model, uint32_t rank, double dig, double range, double offset) {
+    return to_i16((double)model[rank].x * dig / range - offset);
+}
+
 // one sample, FP64 path: float s = nrng(...); raw = s*dig/range - offset  (src/gensig.c:264-270)
 __device__ static inline int16_t sample_exact(uint32_t c1, float m, float sd, double dig, double range, double offset) {
     const double z = box_muller_exact(c1, lcg_mul(c1, LCG_A));

@@ -3,7 +3,7 @@
 //
 //   k_evtab_scan         one workgroup per read over the dwell scan of k_chunks.h (chunk_for_event_tiles) with an origin that spans both chains:
 //                        ev_start from the E the scan carries, and the columns that need no sample -- ev_read, ev_len, seg (k_segments.h's event
-//                        ranges), kmer (k_targets.h's rank, on the event's own chain) and level_raw (src/gensig.c:270).  ev_start and ev_read go
+//                        ranges: seg_ranges), kmer (k_targets.h's rank, on the event's own chain) and level_raw (k_common.h: level_code).  ev_start and ev_read go
 //                        to scratch when the caller does not want them: the reduce pass finds an event's samples through them.
 //   k_evtab_reduce<PA>   a flat grid over the batch's events, one event per lane: a read of 100 events and one of 100 000 load the device alike,
 //                        and no workgroup walks a read's events one behind the other (the label pass's latency chain: profiles/chunks.md).  An event
@@ -12,23 +12,15 @@
 //                        every lane.  An event starts at any sample of the slab, so the loads are the aligned 4-byte words that cover it, their
 //                        halves taken or left (k_chunk_emit's scheme; no misaligned wide load is issued, no word without a sample of the event is
 //                        touched).  mean / sd are derived in the same pass, in FP64 as the header states them.
-// The statistics are k_chunks.h's pass (h_events_table.h runs chunk_stats_run over the whole reads or their inserts).
+// The statistics are k_chunks.h's pass (h_events_table.h runs stats_run over the whole reads or their inserts).
 #pragma once
 
 #define EVT_LANE_MAX 64                              // samples up to which a lane reduces an event alone (33 word loads at the most)
 
 struct EventParams {
-    const ReadDesc* reads;
-    const uint8_t* bases;
-    const float2* model;                             // {level_mean, -}
-    const uint16_t* dwell;                           // the batch's dwells; null: a constant-dwell context, every dwell is const_sps
-    const long long* sig_off;                        // [n_reads+1]
-    const int16_t* sig;                              // the batch's signal slab
+    BatchView bv;
     const float2* consts;                            // [n_reads] {median, 1 / (1.4826 MAD)} (k_chunk_stats); MEDMAD rows only
-    int const_sps, k, meth, rna, n_reads, kind;      // rna: the signal is stored reversed; kind: SEG_NONE / SEG_DNA / SEG_RNA (k_segments.h)
-    int p0, p1;                                      // SEG_DNA: events of the stall, of stall + adaptor.  SEG_RNA: bases of the poly-A, of poly-A + adaptor
     long long n_events;
-    double range, dig;
     long long* ev_start; int* ev_read;               // the caller's or scratch: never null when the reduce pass runs
     int* ev_len; uint32_t* kmer; int16_t* level_raw; uint8_t* seg;                          // the caller's, may be null
     long long* sum; long long* sumsq; int16_t* vmin; int16_t* vmax; float* mean; float* sd;   // the caller's, may be null
@@ -36,30 +28,29 @@ struct EventParams {
 
 __global__ __launch_bounds__(CHUNK_WG) void k_evtab_scan(EventParams Q) {
     __shared__ unsigned long long sh[8];
+    const BatchView& V = Q.bv;
     const int r = blockIdx.x;
-    const ReadDesc rd = Q.reads[r];
-    const long long n = Q.sig_off[r + 1] - Q.sig_off[r];
-    const int ne0 = rd.ne0, ne = rd.ne0 + max(rd.ne1, 0);
-    // the event ranges of include/sqg_segments.h: DNA [0, a) stall, [a, b) adaptor, then insert; RNA [0, a) insert, [a, b) poly-A, [b, ne0) adaptor, chain 1 stall
-    int a = 0, b = 0;
-    if (Q.kind == SEG_DNA) { a = min(Q.p0, ne0); b = min(Q.p1, ne0); }
-    else if (Q.kind == SEG_RNA) { const int len = max(rd.len0 - Q.p1, 0); a = min(len, ne0); b = min(len + Q.p0, ne0); }
-    const uint8_t* bp0 = Q.bases + rd.base_off;
+    const ReadDesc rd = V.reads[r];
+    const long long n = V.sig_off[r + 1] - V.sig_off[r];
+    const int ne0 = rd.ne0, ne = rd.ne0 + max(rd.ne1, 0), kind = V.kind;
+    const SegRanges sr = seg_ranges(V, rd);
+    const int a = sr.a, b = sr.b;
+    const uint8_t* bp0 = V.bases + rd.base_off;
     const uint8_t* bp1 = bp0 + rd.len0 - ne0;               // chain 1's event e has its k-mer at bp0 + len0 + (e - ne0)
-    chunk_for_event_tiles(ChunkOrigin{rd.ev_off, rd.base_off, ne}, Q.dwell, Q.const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
+    chunk_for_event_tiles(ChunkOrigin{rd.ev_off, rd.base_off, ne}, V.dwell, V.const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int e = e0 + q;
             if (e < ne) {
                 const long long at = rd.ev_off + e;
-                if (Q.ev_start) Q.ev_start[at] = Q.rna ? n - (long long)E - d[q] : (long long)E;
+                if (Q.ev_start) Q.ev_start[at] = V.rna ? n - (long long)E - d[q] : (long long)E;
                 if (Q.ev_read) Q.ev_read[at] = r;
                 if (Q.ev_len) Q.ev_len[at] = d[q];
-                if (Q.seg) Q.seg[at] = (uint8_t)(Q.kind == SEG_DNA ? (e < a ? 0 : e < b ? 1 : 3) : Q.kind == SEG_RNA ? (e < a ? 3 : e < b ? 2 : e < ne0 ? 1 : 0) : 3);
+                if (Q.seg) Q.seg[at] = (uint8_t)(kind == SEG_DNA ? (e < a ? 0 : e < b ? 1 : 3) : kind == SEG_RNA ? (e < a ? 3 : e < b ? 2 : e < ne0 ? 1 : 0) : 3);
                 if (Q.kmer || Q.level_raw) {
-                    const uint32_t rank = kmer_rank_wide((e < ne0 ? bp0 : bp1) + e, Q.k, Q.meth);
+                    const uint32_t rank = kmer_rank_wide((e < ne0 ? bp0 : bp1) + e, V.k, V.meth);
                     if (Q.kmer) Q.kmer[at] = rank;
-                    if (Q.level_raw) Q.level_raw[at] = to_i16((double)Q.model[rank].x * Q.dig / Q.range - rd.offset);      // src/gensig.c:270
+                    if (Q.level_raw) Q.level_raw[at] = level_code(V.model, rank, V.dig, V.range, rd.offset);
                 }
             }
             E += (unsigned long long)d[q];
@@ -113,6 +104,14 @@ __device__ __forceinline__ EventAcc evtab_take(const uint32_t* W, const bool tak
     return A;
 }
 
+// Event i of a flat grid over the batch's events: its read, its samples and the first of them in the slab (through the scan pass's ev_read
+// and ev_start).  k_evtab_reduce and k_pileup.
+struct EventAt { int r, len; long long s0; };
+__device__ __forceinline__ EventAt evtab_event(const EventParams& Q, const long long i) {
+    const int r = Q.ev_read[i];
+    return {r, Q.bv.dwell ? (int)Q.bv.dwell[i] : Q.bv.const_sps, Q.bv.sig_off[r] + Q.ev_start[i]};
+}
+
 // mean / sd of an event of read r from its sums, as include/sqg_events.h states them: one rounding per operation (the build has
 // -ffp-contract=off); double sqrt is correctly rounded on this device, as the exact sample path relies on (k_common.h: box_muller_exact)
 template <bool PA>
@@ -123,9 +122,9 @@ __device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, 
     v = v < 0 ? 0 : v;
     const double s = sqrt(v);
     if (PA) {
-        const double offset = Q.reads[r].offset;
-        *mean = (float)(((m + offset) * Q.range) / Q.dig);
-        *sd = (float)((s * Q.range) / Q.dig);
+        const double offset = Q.bv.reads[r].offset;
+        *mean = (float)(((m + offset) * Q.bv.range) / Q.bv.dig);
+        *sd = (float)((s * Q.bv.range) / Q.bv.dig);
     } else {
         const float2 cs = Q.consts[r];                                   // cs.x = med2 / 2 exactly: |med2| < 2^17
         *mean = (float)((m - (double)cs.x) * (double)cs.y);
@@ -136,17 +135,11 @@ __device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, 
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_evtab_reduce(EventParams Q) {
     const int lane = threadIdx.x & 63;
-    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.sig);              // the slab in aligned words: sample s is half s & 1 of word s >> 1
+    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.bv.sig);              // the slab in aligned words: sample s is half s & 1 of word s >> 1
     for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
         const long long i = base + threadIdx.x;
         const bool have = i < Q.n_events;
-        int r = 0, len = 0;
-        long long s0 = 0;                                                        // the event's first sample in the slab
-        if (have) {
-            r = Q.ev_read[i];
-            len = Q.dwell ? (int)Q.dwell[i] : Q.const_sps;
-            s0 = Q.sig_off[r] + Q.ev_start[i];
-        }
+        const auto [r, len, s0] = have ? evtab_event(Q, i) : EventAt{0, 0, 0};
         const EventAcc A = evtab_take(W, have, len, s0, lane);
         if (!have) continue;
         if (Q.sum) Q.sum[i] = A.sum;

@@ -1,7 +1,7 @@
 // k_pileup.h -- the events of a batch added, across reads, into per-key sums the caller keeps from batch to batch (include/sqg_pileup.h)
 // Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_events_table.h, whose scan pass and sample reduction it uses.
 //
-//   k_pileup<PA>   k_evtab_reduce's grid: a flat grid over the batch's events, one event per lane, the samples taken by evtab_take and mean / sd
+//   k_pileup<PA>   k_evtab_reduce's grid: a flat grid over the batch's events, one event per lane (evtab_event), the samples taken by evtab_take and mean / sd
 //                  derived by evtab_derive -- the very code of the event table, so q(mean) is q of the float the table holds.  Whether an event
 //                  counts and where is decided BEFORE its samples are loaded: an event outside the key window costs its descriptor and no sample.
 //                  No per-event column is written.  The adds are no-return relaxed integer atomics at agent scope; consecutive lanes hold
@@ -27,26 +27,23 @@ __device__ __forceinline__ long long pileup_q(const float x) { return (long long
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams U) {
     const int lane = threadIdx.x & 63;
-    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.sig);
+    const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.bv.sig);
     const long long width = U.hi - U.lo;
     const bool want_samples = U.mean_sum || U.mean_sq || U.sd_sum;
     for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
         const long long i = base + threadIdx.x;
         const bool have = i < Q.n_events;
-        int r = 0, len = 0;
-        long long s0 = 0, key = 0;
+        const auto [r, len, s0] = have ? evtab_event(Q, i) : EventAt{0, 0, 0};
+        long long key = 0;
         bool eligible = false;
         int plane = 0;
         if (have) {
-            r = Q.ev_read[i];
-            len = Q.dwell ? (int)Q.dwell[i] : Q.const_sps;
-            s0 = Q.sig_off[r] + Q.ev_start[i];
             const PileRead pr = U.pr[r];
             if (U.by_kmer) {
                 eligible = pr.step != 0 && ((U.segs >> U.seg[i]) & 1u);
                 key = (long long)U.kmer[i];
             } else {
-                const ReadDesc rd = Q.reads[r];
+                const ReadDesc rd = Q.bv.reads[r];
                 const long long e = i - rd.ev_off;
                 const long long j = e - pr.first;
                 eligible = pr.step != 0 && e < rd.ne0 && j >= 0 && j <= (long long)pr.L - U.k;

@@ -6,12 +6,11 @@
 //                        event order by a second workgroup scan with a carry from tile to tile.  MODE 0 writes the read's count (the plan);
 //                        MODE 1 one record per site at site_off[r] + rank, and site_read / site_pos / win_start / label for the caller.  No
 //                        per-event array is made.
-//   k_site_emit<F32, PA> one wavefront per site at a time.  The signal row through k_chunks.h's normalisation and 16-byte row stores; the
-//                        window starts at any sample of the read, so the loads are the aligned 4-byte words that cover a lane's 8 samples,
-//                        shifted (k_chunk_emit's scheme; no misaligned wide load is issued).  context straight from the bases.  ctx_start
+//   k_site_emit<F32, PA> one wavefront per site at a time.  The signal row through k_chunks.h's row function (chunk_row8: the window starts
+//                        at any sample of the read), a lane 8 samples.  context straight from the bases.  ctx_start
 //                        needs no global prefix sum: E[a] = w0 + before is known, and the at most 256 boundaries around it are a prefix
 //                        sum, inside the wavefront, of the dwells on either side of a.
-// The statistics are k_chunks.h's pass over the whole reads (h_sites.h runs chunk_stats_run).
+// The statistics are k_chunks.h's pass over the whole reads (h_sites.h runs stats_run).
 #pragma once
 
 #define SITE_CTX_SEGS 4                              // 64-entry steps of a ctx_start row: B + 1 <= 256 entries
@@ -22,37 +21,32 @@ struct SiteRec {                                     // 16 bytes
 };
 
 struct SiteParams {
-    const ReadDesc* reads;
-    const uint8_t* bases;
-    const uint16_t* dwell;                           // the batch's dwells; null: a constant-dwell context, every dwell is const_sps
-    const long long* sig_off;                        // [n_reads+1]
+    BatchView bv;
     const uint8_t* skip;                             // [n_reads] 1: a read shorter than a k-mer (its stand-in sequence has no sites); null: none is
-    int const_sps, meth, n_reads;
     int L, before, focus, B, cb;
     int* count;                                      // [n_reads] MODE 0: sites of every read
     const long long* site_off;                       // [n_reads+1] MODE 1 and the emit: first site of every read
     long long n_sites;
     SiteRec* rec;                                    // [n_sites]
     uint8_t* label; int* site_read; int* site_pos; long long* win_start;   // the caller's, may be null
-    const int16_t* sig;                              // the batch's signal slab
     const float2* consts;                            // [n_reads] {median, 1 / (1.4826 MAD)} (k_chunk_stats)
-    double range, dig;
     void* signal; uint8_t* context; int* ctx_start;  // the caller's, may be null
 };
 
 template <int MODE>
 __global__ __launch_bounds__(CHUNK_WG) void k_site_scan(SiteParams Q) {
     __shared__ unsigned long long sh[8];
+    const BatchView& V = Q.bv;
     const int r = blockIdx.x;
     if (Q.skip && Q.skip[r]) { if (MODE == 0 && threadIdx.x == 0) Q.count[r] = 0; return; }
-    const ReadDesc rd = Q.reads[r];
-    const long long n = Q.sig_off[r + 1] - Q.sig_off[r];
-    const int ne = rd.ne0, len = rd.len0, f = Q.focus, meth = Q.meth;
-    const uint8_t* bp = Q.bases + rd.base_off;
+    const ReadDesc rd = V.reads[r];
+    const long long n = V.sig_off[r + 1] - V.sig_off[r];
+    const int ne = rd.ne0, len = rd.len0, f = Q.focus, meth = V.meth;
+    const uint8_t* bp = V.bases + rd.base_off;
     const long long first = MODE ? Q.site_off[r] : 0;
     const long long before = Q.before, L = Q.L;
     unsigned long long ranked = 0;                          // sites of the tiles so far
-    chunk_for_event_tiles(ChunkOrigin{rd.ev_off, rd.base_off, ne}, Q.dwell, Q.const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
+    chunk_for_event_tiles(ChunkOrigin{rd.ev_off, rd.base_off, ne}, V.dwell, V.const_sps, sh, [&](int e0, unsigned long long E, const int (&d)[4]) {
         unsigned int fit = 0;
         uint8_t b0[4];
         long long w0[4];
@@ -90,40 +84,24 @@ __global__ __launch_bounds__(CHUNK_WG) void k_site_scan(SiteParams Q) {
 // A workgroup takes CHUNK_WG / 64 sites at a time, one per wavefront (every loop bound below is the same for the lanes of a wavefront).
 template <bool F32, bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_site_emit(SiteParams Q) {
+    const BatchView& V = Q.bv;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int per = CHUNK_WG / 64, g8 = Q.L >> 3, B = Q.B, cb = Q.cb;
     for (long long s = (long long)blockIdx.x * per + wv; s < Q.n_sites; s += (long long)gridDim.x * per) {
         const SiteRec sr = Q.rec[s];
         const int r = sr.read;
-        const ReadDesc rd = Q.reads[r];
+        const ReadDesc rd = V.reads[r];
         if (Q.signal) {
-            const int16_t* src0 = Q.sig + Q.sig_off[r] + sr.w0;
+            const int16_t* src0 = V.sig + V.sig_off[r] + sr.w0;
             const float2 cs = PA ? make_float2(0.f, 0.f) : Q.consts[r];          // (PA: no statistics pass has run)
             const double offset = PA ? rd.offset : 0.0;
-            for (int w = lane; w < g8; w += 64) {
-                const int16_t* src = src0 + (long long)w * 8;
-                const uint32_t* q = reinterpret_cast<const uint32_t*>((uintptr_t)src & ~(uintptr_t)3);
-                const bool odd = ((uintptr_t)src & 2) != 0;
-                uint32_t a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
-                if (odd) {
-                    const uint32_t a4 = q[4];
-                    a0 = (a0 >> 16) | (a1 << 16); a1 = (a1 >> 16) | (a2 << 16); a2 = (a2 >> 16) | (a3 << 16); a3 = (a3 >> 16) | (a4 << 16);
-                }
-                const uint32_t a[4] = {a0, a1, a2, a3};
-                float x[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int raw = (int)(int16_t)((a[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-                    x[i] = PA ? chunk_norm_pa(raw, offset, Q.range, Q.dig) : chunk_norm_medmad(raw, cs);
-                }
-                chunk_store8<F32>(Q.signal, s * (long long)Q.L + (long long)w * 8, x);
-            }
+            for (int w = lane; w < g8; w += 64) chunk_row8<F32, PA>(V, src0 + (long long)w * 8, cs, offset, Q.signal, s * (long long)Q.L + (long long)w * 8);
         }
         if (Q.context) {
             uint8_t* row = Q.context + s * (long long)B;
             for (int i = lane; i < B; i += 64) {
                 const int pos = sr.p - cb + i;
-                row[i] = (pos >= 0 && pos < rd.len0) ? (uint8_t)chunk_label_code(Q.bases[rd.base_off + pos], Q.meth) : (uint8_t)0;
+                row[i] = (pos >= 0 && pos < rd.len0) ? (uint8_t)chunk_label_code(V.bases[rd.base_off + pos], V.meth) : (uint8_t)0;
             }
         }
         if (Q.ctx_start) {
@@ -136,7 +114,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_site_emit(SiteParams Q) {
                 S[g] = 0;
                 if (g >= segs) continue;
                 const int i = 64 * g + lane, e = ea + i;
-                const int v = (i < B && e >= 0 && e < ne) ? (Q.dwell ? (int)Q.dwell[rd.ev_off + e] : Q.const_sps) : 0;
+                const int v = (i < B && e >= 0 && e < ne) ? (V.dwell ? (int)V.dwell[rd.ev_off + e] : V.const_sps) : 0;
                 int inc = v;
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) {

@@ -21,21 +21,17 @@
 #define TGT_SPT 16                        // samples per thread: a row of moves leaves in 16-byte stores
 #define TGT_TILE (CHUNK_WG * TGT_SPT)     // samples per workgroup and pass
 
-struct TargetParams {
-    const ReadDesc* reads;
-    const uint8_t* bases;
-    const float2* model;                  // {level_mean, -}
+struct TargetParams {                     // beside the job's ChunkParams
     const uint32_t* ev_start;             // [n_events] pass A's output; null: constant dwell
-    int k, meth, rna, const_sps;
     void* clean; int16_t* clean_raw; uint8_t* moves; uint32_t* kmer;
 };
 
-__global__ __launch_bounds__(CHUNK_WG) void k_target_scan(ChunkParams P, const ReadDesc* __restrict__ reads, const uint16_t* __restrict__ dwell,
-                                                          uint32_t* __restrict__ ev_start) {
+__global__ __launch_bounds__(CHUNK_WG) void k_target_scan(ChunkParams P, uint32_t* __restrict__ ev_start) {
     __shared__ unsigned long long sh[8];
     const int r = blockIdx.x;
     if (P.chunk_off[r + 1] == P.chunk_off[r]) return;       // no chunk asks for this read's events
-    const ChunkOrigin og = chunk_origin(P, reads[r], r);
+    const ChunkOrigin og = chunk_origin(P, P.bv.reads[r], r);
+    const uint16_t* __restrict__ dwell = P.bv.dwell;
     __builtin_assume(dwell != nullptr);                     // (the host launches this pass in dwell-stream contexts only)
     chunk_for_event_starts(og, dwell, 0, sh, [&](int e, unsigned long long E, int) {
         ev_start[og.ev_off + e] = (uint32_t)E;              // (the host has checked: the read has at most UINT32_MAX samples)
@@ -80,6 +76,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
     __shared__ uint32_t ev_rank[KMER ? EV_N : 1];
     __shared__ int ev_code[RAW ? EV_N : 1];
     __shared__ float ev_x[CLEAN != 0 ? EV_N : 1];
+    const BatchView& V = P.bv;
     const int t = threadIdx.x;
     const auto [n_tiles, tpc, cpb] = tgt_geom(P.L);
     const int sub = t / tpc, w0 = t - sub * tpc;
@@ -97,19 +94,19 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
             tl = (int)(item - c * n_tiles);
             r = P.chunk_read[c];
             const long long j = c - P.chunk_off[r], n = P.hi[r] - P.lo[r];
-            gt0 = (T.rna ? n - j * P.S - P.L : j * P.S) + (long long)tl * TGT_TILE;        // the tile's first generation-order sample
+            gt0 = (V.rna ? n - j * P.S - P.L : j * P.S) + (long long)tl * TGT_TILE;        // the tile's first generation-order sample
             tlen = min(TGT_TILE, P.L - tl * TGT_TILE);
-            const ReadDesc rd = T.reads[r];
+            const ReadDesc rd = V.reads[r];
             const ChunkOrigin og = chunk_origin(P, rd, r);
             ne = og.ne; ev_off = og.ev_off; base_off = og.base_off; offset = rd.offset;
             if (T.ev_start) { E = T.ev_start + ev_off; e_lo = tgt_lower_bound(E, ne, (uint32_t)gt0); }
-            else e_lo = (int)min((gt0 + T.const_sps - 1) / T.const_sps, (long long)ne);
+            else e_lo = (int)min((gt0 + V.const_sps - 1) / V.const_sps, (long long)ne);
         }
         __syncthreads();
         if (active) {
             const long long gt1 = gt0 + tlen;
             for (int e = e_lo + w0; e < ne; e += tpc) {
-                const long long v = E ? (long long)E[e] : (long long)e * T.const_sps;
+                const long long v = E ? (long long)E[e] : (long long)e * V.const_sps;
                 if (v >= gt1) break;
                 const int x = (int)(v - gt0);               // 0 <= x < tlen <= 16 tpc: inside this chunk's 4 tpc words
                 atomicOr(&mark[4 * sub * tpc + (x >> 2)], 1u << (8 * (x & 3)));
@@ -131,13 +128,13 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
                 if (CLEAN != 0 && !PA) cs = P.consts[r];
                 for (int q = w0; q < nq; q += tpc) {
                     const int ec = min(max(e_lo - 1 + q, 0), ne - 1);          // (every index stays inside the read)
-                    const uint32_t rank = kmer_rank_wide(T.bases + base_off + ec, T.k, T.meth);
+                    const uint32_t rank = kmer_rank_wide(V.bases + base_off + ec, V.k, V.meth);
                     const int at = sub * (TGT_SPT * tpc + 1) + q;
                     if (KMER) ev_rank[at] = rank;
                     if (CLEAN != 0 || RAW) {
-                        const int code = (int)to_i16((double)T.model[rank].x * P.dig / P.range - offset);      // src/gensig.c:270
+                        const int code = (int)level_code(V.model, rank, V.dig, V.range, offset);
                         if (RAW) ev_code[at] = code;
-                        if (CLEAN != 0) ev_x[at] = PA ? chunk_norm_pa(code, offset, P.range, P.dig) : chunk_norm_medmad(code, cs);
+                        if (CLEAN != 0) ev_x[at] = PA ? chunk_norm_pa(code, offset, V.range, V.dig) : chunk_norm_medmad(code, cs);
                     }
                 }
             }
@@ -158,8 +155,8 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
                     rr[i] = RAW ? ev_code[q] : 0; kk[i] = KMER ? ev_rank[q] : 0u; xx[i] = CLEAN != 0 ? ev_x[q] : 0.f;
                 }
                 const int xg = xc + 8 * grp;
-                const long long at = c * (long long)P.L + (T.rna ? P.L - 8 - xg : xg);
-                if (T.rna) {
+                const long long at = c * (long long)P.L + (V.rna ? P.L - 8 - xg : xg);
+                if (V.rna) {
 #pragma unroll
                     for (int i = 0; i < 4; i++) {
                         const int a = rr[i]; rr[i] = rr[7 - i]; rr[7 - i] = a;
@@ -185,9 +182,9 @@ __global__ __launch_bounds__(CHUNK_WG) void k_target_emit(ChunkParams P, TargetP
             // the bytes of LDS are the row; RNA: in reverse.  One 16-byte store where the row's address allows (always when L is a multiple
             // of 16 and the array is 16-byte aligned), else 8-byte ones -- the interface asks for 8-byte alignment only.
             const int len = two ? 16 : 8;
-            uint8_t* dst = T.moves + c * (long long)P.L + (T.rna ? P.L - len - xc : xc);
+            uint8_t* dst = T.moves + c * (long long)P.L + (V.rna ? P.L - len - xc : xc);
             uint32_t w[4];
-            if (!T.rna) { w[0] = m4[0]; w[1] = m4[1]; w[2] = m4[2]; w[3] = m4[3]; }
+            if (!V.rna) { w[0] = m4[0]; w[1] = m4[1]; w[2] = m4[2]; w[3] = m4[3]; }
             else if (two) { w[0] = __builtin_bswap32(m4[3]); w[1] = __builtin_bswap32(m4[2]); w[2] = __builtin_bswap32(m4[1]); w[3] = __builtin_bswap32(m4[0]); }
             else { w[0] = __builtin_bswap32(m4[1]); w[1] = __builtin_bswap32(m4[0]); w[2] = 0u; w[3] = 0u; }
             if (two && ((uintptr_t)dst & 15u) == 0) *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);

@@ -1,0 +1,120 @@
+"""The calls that read a finished batch on the device share scratch of the context (the reads' constants, the inserts' spans, the chunk
+and site plans, the event columns): what a call writes must not depend on which other calls ran before it on that context.  Every call
+alone on a fresh context is the reference; the same calls in the listed order, in reverse, and across two consecutive batches -- those
+for batch 0 made after batch 1 has run, while batch 0 still owns its device results -- must give the same tensors, bit for bit."""
+import numpy as np
+import pytest
+import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
+
+from chunk_support import _context, _fixture_reads
+from refvec_cases import REFVEC_CASES
+from squigulator_amd import api
+
+L, S, W = 64, 8, 16
+
+
+def _pileup(b, origin=None, **kw):
+    p = b.gen.new_pileup(**kw)
+    counted, outside = b.pileup(p, origin=origin)
+    return api.Chunks(counted=counted, outside=outside, **{n: getattr(p, n) for n in api.PILEUP_OUTPUTS})
+
+
+def _segments(b):
+    seg, shift = b.segments()
+    return api.Chunks(seg=seg, shift=shift)
+
+
+def _origin(b):
+    """one origin per read, the second on the minus strand; the window [200, 4000) leaves events of every read outside"""
+    n = b.n_reads
+    return (200 * np.arange(n, dtype=np.int64) + np.where(np.arange(n) & 1, 5000, 100)), np.where(np.arange(n) & 1, -1, 1).astype(np.int8)
+
+
+JOBS = {
+    # DNA, no prefix, SQG_METH
+    "r9_meth": [
+        ("chunks", lambda b: b.chunks(L, S, W)),
+        ("chunk_targets", lambda b: b.chunk_targets(L, S, clean=True, clean_raw=True, moves=True, kmer=True)),
+        ("sites", lambda b: b.sites(64, ctx_len=5)),
+        ("events medmad", lambda b: b.events("medmad")),
+        ("events pa", lambda b: b.events("pa")),
+        ("pileup ref medmad", lambda b: _pileup(b, origin=_origin(b), by="ref", norm="medmad", lo=200, hi=4000)),
+    ],
+    # RNA, SQG_PREFIX
+    "rna004_prefix": [
+        ("segments", _segments),
+        ("chunks trim", lambda b: b.chunks(L, S, W, trim=True)),
+        ("chunk_targets trim", lambda b: b.chunk_targets(L, S, clean=True, clean_raw=True, moves=True, kmer=True, trim=True)),
+        ("events medmad trim", lambda b: b.events("medmad", trim=True)),
+        ("events medmad", lambda b: b.events("medmad", trim=False)),
+        ("pileup kmer trim", lambda b: _pileup(b, by="kmer", norm="medmad", trim=True)),
+    ],
+}
+
+
+def _batches(cid, mode, n_batches):
+    """a fresh context with the fixture's reads run as n_batches consecutive batches (the same reads each time: the generator's state moves
+    on, so the batches' signals differ), all waited for"""
+    _, _, gen = _context(dict(REFVEC_CASES)[cid], mode)
+    seqs = [r["seq"] for r in _fixture_reads(cid)]
+    bs = [gen.stage(seqs).run() for _ in range(n_batches)]
+    return gen, [b.wait() for b in bs]
+
+
+def _close(gen, bs):
+    for b in bs:
+        b.free()
+    gen.close()
+
+
+def _same(got, want, what):
+    assert vars(got).keys() == vars(want).keys(), what
+    n = 0
+    for key, w in vars(want).items():
+        g = getattr(got, key)
+        if isinstance(w, torch.Tensor):
+            assert isinstance(g, torch.Tensor) and g.dtype == w.dtype and torch.equal(g.cpu(), w.cpu()), f"{what}: {key}"
+            n += w.numel()
+        elif isinstance(w, np.ndarray):
+            assert np.array_equal(g, w), f"{what}: {key}"
+        else:
+            assert g == w, f"{what}: {key}"
+    return n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [api.MODE_CERTIFIED, api.MODE_EXACT], ids=["certified", "exact"])
+@pytest.mark.parametrize("cid", list(JOBS))
+def test_outputs_do_not_depend_on_the_calls_before(cid, mode):
+    calls = JOBS[cid]
+    alone = {}
+    for bi in (0, 1):
+        for name, call in calls:
+            gen, bs = _batches(cid, mode, bi + 1)
+            alone[(bi, name)] = call(bs[bi])
+            _close(gen, bs)
+    for name, _ in calls:                                  # the reference says something: rows were written, and the two batches differ
+        a0, a1 = alone[(0, name)], alone[(1, name)]
+        assert sum(t.numel() for t in vars(a0).values() if isinstance(t, torch.Tensor)) > 0, name
+        if name == "segments":                             # (rna004-prom has dwell_std 0: the segments, dwell sums, are the same in every batch)
+            continue
+        assert any(isinstance(t, torch.Tensor) and (t.shape != getattr(a1, k).shape or not torch.equal(t, getattr(a1, k))) for k, t in vars(a0).items()), name
+    assert alone[(0, calls[-1][0])].counted > 0
+    if cid == "r9_meth":
+        assert alone[(0, "pileup ref medmad")].outside > 0
+    else:                                                  # the trimmed job took the inserts' spans: the same sums, other statistics
+        t, w = alone[(0, "events medmad trim")], alone[(0, "events medmad")]
+        assert torch.equal(t.sum, w.sum) and not torch.equal(t.med2, w.med2) and not torch.equal(t.mean, w.mean)
+    for what, order in (("listed order", calls), ("reverse order", calls[::-1])):
+        gen, bs = _batches(cid, mode, 1)
+        for name, call in order:
+            assert _same(call(bs[0]), alone[(0, name)], f"{cid} {what}: {name}") > 0
+        _close(gen, bs)
+    # two batches: both have run before the first call; every call on batch 1, then on batch 0 (the shared scratch changes hands each time)
+    gen, bs = _batches(cid, mode, 2)
+    for name, call in calls:
+        for bi in (1, 0):
+            _same(call(bs[bi]), alone[(bi, name)], f"{cid} two batches: {name} on batch {bi}")
+    for name, call in calls[::-1]:                         # ... and every call on batch 0 once more, with batch 1's scratch left behind
+        _same(call(bs[0]), alone[(0, name)], f"{cid} two batches, again: {name} on batch 0")
+    _close(gen, bs)

@@ -214,7 +214,7 @@ def _assert_rows_behind_cap(got, want, keys, cap, n, what):
 @pytest.mark.gpu
 @pytest.mark.parametrize("norm", ["pa", "medmad"])
 def test_events_behind_the_first_trip_of_the_grid(norm):
-    """k_events_table.h:140, `base += gridDim.x * CHUNK_WG` of k_evtab_reduce: its second trip, which no earlier test takes (their
+    """k_events_table.h:139, `base += gridDim.x * CHUNK_WG` of k_evtab_reduce: its second trip, which no earlier test takes (their
     batches hold a few thousand events, one trip covers 32 * CUs * 256).  Behind cap the batch has dwells of 1, 63, 64, 65 and above 128
     and a wavefront with both kinds, so evtab_take's lane loop and its ballot / shuffle loop both run there, in one wavefront too; the
     last wavefront is partly empty (n_events is no multiple of 64), and `if (!have) continue` at line 151 is met on the second trip.  All
@@ -247,7 +247,7 @@ def test_events_behind_the_first_trip_of_the_grid(norm):
 
 @pytest.mark.gpu
 def test_constant_dwell_events_behind_the_first_trip():
-    """k_events_table.h:147, the `Q.dwell == nullptr` branch (SQG_IDEAL_TIME) on the second trip of k_evtab_reduce, in the development
+    """k_events_table.h:112, the `Q.dwell == nullptr` branch (SQG_IDEAL_TIME) on the second trip of k_evtab_reduce, in the development
     build of the library: every dwell is 65, so behind cap every lane's event is reduced by its wavefront (evtab_take's ballot is full on a
     trip no earlier test takes, and partly empty in the last wavefront).  The samples are signal_cases' `uniform`: all of int16"""
     cap = _device_cap()
@@ -310,8 +310,8 @@ def _laid_over_a_span(lens, k, width, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("norm", ["pa", "medmad"])
 def test_pileup_behind_the_first_trip_of_the_grid(norm):
-    """k_pileup.h:33, `base += gridDim.x * CHUNK_WG` of k_pileup: its second trip, with the two ballots of line 66 and the `continue`
-    of line 71 on it, which no earlier test takes.  The drawn-dwell batch of the event test under a caller's origin that lays 600 reads
+    """k_pileup.h:33, `base += gridDim.x * CHUNK_WG` of k_pileup: its second trip, with the two ballots of line 63 and the `continue`
+    of line 68 on it, which no earlier test takes.  The drawn-dwell batch of the event test under a caller's origin that lays 600 reads
     over some 9000 keys, half of them backwards (a few hundred adds per key), by position with a window that cuts the span at both ends
     and by pore-table row with a window over half the rows: events behind cap are counted and are outside, so evtab_take gets lanes that
     are taken and lanes that are not next to long events there.  All six outputs against pileup_ref over the batch's event table (which
@@ -352,7 +352,7 @@ def test_pileup_behind_the_first_trip_of_the_grid(norm):
 
 @pytest.mark.gpu
 def test_pileup_keys_beyond_32_bits_and_below_zero():
-    """k_pileup.h:53 and 63, `key = pr.key0 + step * j` and the window comparison, and :72, `key - U.lo`, with keys that need more than
+    """k_pileup.h:50 and 60, `key = pr.key0 + step * j` and the window comparison, and :69, `key - U.lo`, with keys that need more than
     32 bits (hg38 laid end to end passes 2^31 at chr13) and with negative ones: every earlier key is below 30 000.  A caller's origin is
     shifted by 2^31 - 150, 2^32 - 150, 2^40 + 7, -150 and -2^33 - 150 together with a window that cuts reads at both ends and straddles the
     power of two (or 0): the six arrays of both strand planes and (counted, outside) must be those of the unshifted call, which is
@@ -430,7 +430,7 @@ def _revcomp(s):
 
 @pytest.mark.gpu
 def test_the_sampler_origin_on_four_contigs_and_both_strands():
-    """h_pileup.h:68, `h_contig_off[ref_idx] + ref_pos + (minus ? rlen - k : 0)`, with a contig offset that is not 0 on both strands: the
+    """h_pileup.h:58, `h_contig_off[ref_idx] + ref_pos + (minus ? rlen - k : 0)`, with a contig offset that is not 0 on both strands: the
     DNA tests load one contig, the sequin test has '+' reads only, so the '-' rule on a later contig rested on pileup_ref.sampler_origin,
     which states the same formula.  Here the origin is not restated: every read's text (or its reverse complement) is found in the
     contigs laid end to end with bytes.find, and the whole-genome n of the pileup is the coverage of the k-mers of those matches, per
@@ -479,8 +479,8 @@ def test_the_sampler_origin_on_four_contigs_and_both_strands():
 @pytest.mark.gpu
 @pytest.mark.parametrize("dwell", [LANE_MAX + 1, 5000])
 def test_long_events_beside_lanes_that_are_not_taken(dwell):
-    """k_pileup.h:65, `evtab_take(W, inside && ..., ...)` with `take` false in some lanes of a wavefront whose other lanes hold events
-    longer than EVT_LANE_MAX: evtab_take's ballot (k_events_table.h:90) then has holes, and the lanes that are not taken still load and
+    """k_pileup.h:62, `evtab_take(W, inside && ..., ...)` with `take` false in some lanes of a wavefront whose other lanes hold events
+    longer than EVT_LANE_MAX: evtab_take's ballot (k_events_table.h:81) then has holes, and the lanes that are not taken still load and
     shuffle for their neighbours.  The earlier constant-dwell test has all 76 events inside the window.  Dwells of 65 and 5000; by row with
     a window over a scattered subset of the events, and by position with a window that takes events 10 .. 40 of the 70-event read; the
     outputs against np.add.at over the columns of the event table"""
