@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h and include/sqg_pileup.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h and include/sqg_detect.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -173,6 +173,21 @@ class CPileupStat(C.Structure):
     _fields_ = [("counted", C.c_int64), ("outside", C.c_int64)]
 
 
+# include/sqg_detect.h: bound the same way
+EXPORTS_DETECT = ("sqg_detect_plan", "sqg_batch_detect")
+DETECT_OUTPUTS = ("dt_read", "dt_start", "dt_len", "sum", "sumsq", "vmin", "vmax", "mean", "sd", "true_ev", "med2", "mad4")
+DETECT_PRESETS = {"dna": (3, 6, 1.4, 9.0, 0.2), "rna": (7, 14, 2.5, 9.0, 1.0)}        # SQG_DETECT_DNA, SQG_DETECT_RNA
+
+
+class CDetectCfg(C.Structure):
+    _fields_ = [("w_short", C.c_int32), ("w_long", C.c_int32), ("thr_short", C.c_double), ("thr_long", C.c_double), ("peak_height", C.c_double),
+                ("norm", C.c_uint32), ("trim", C.c_int32)]
+
+
+class CDetectOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in DETECT_OUTPUTS]
+
+
 class Pileup:
     """What SignalGenerator.new_pileup() returns: the cfg of a pileup and its sums, torch tensors [planes, hi - lo] on the context's device
     that Batch.pileup() adds to (include/sqg_pileup.h says what they hold); those not asked for are None"""
@@ -198,6 +213,7 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_SITES, {"sqg_site_plan": (CSiteCfg,) + _PLAN, "sqg_batch_sites": (CSiteCfg, CSiteOut)}),
     (EXPORTS_EVENTS, {"sqg_batch_events": (CEventCfg, CEventOut)}),
     (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
+    (EXPORTS_DETECT, {"sqg_detect_plan": (CDetectCfg,) + _PLAN, "sqg_batch_detect": (CDetectCfg, CDetectOut)}),
 )
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
@@ -731,6 +747,47 @@ class Batch:
         torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
         self.gen._chk(self.gen.L.sqg_batch_events(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_events")
         return ev
+
+    def _detect_cfg(self, cfg, norm, trim):
+        _need(self.gen.L, "sqg_batch_detect", "sqg_detect.h", "detect")
+        nm, = _enum("detect", norm=norm)
+        five = DETECT_PRESETS.get(cfg, cfg) if isinstance(cfg, str) else cfg
+        if isinstance(five, str) or len(five) != 5:
+            raise SqgError(-1, "detect", f"cfg must be one of {sorted(DETECT_PRESETS)} or (w_short, w_long, thr_short, thr_long, peak_height), not {cfg!r}")
+        return CDetectCfg(int(five[0]), int(five[1]), float(five[2]), float(five[3]), float(five[4]), nm, int(trim))
+
+    def detect_plan(self, cfg="dna"):
+        """(det_off [n_reads+1], n_rows): the first row of every read in the table Batch.detect() makes with the same cfg
+        (sqg_detect_plan, include/sqg_detect.h; device work and a copy-back of the per-read counts)"""
+        return self._detect_plan(self._detect_cfg(cfg, "pa", False))
+
+    def _detect_plan(self, cfg):
+        off = np.zeros(self.n_reads + 1, np.int64)
+        nr = C.c_int64()
+        self.gen._chk(self.gen.L.sqg_detect_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nr)), "sqg_detect_plan")
+        return off, int(nr.value)
+
+    def detect(self, cfg="dna", norm="pa", trim: bool = False, outputs=None) -> Chunks:
+        """The table a raw-signal tool's event detector finds in the batch's stored samples, made on the device (sqg_batch_detect,
+        include/sqg_detect.h): the two-window t-statistic detector of scrappie / f5c with exact integer window sums.  cfg: "dna", "rna"
+        or (w_short, w_long, thr_short, thr_long, peak_height).  torch tensors [n_rows]: dt_read (int32), dt_start (int64: first stored
+        sample within the read), dt_len (int32), sum, sumsq (int64), vmin, vmax (int16), mean, sd (float32, normalised by norm: "pa"
+        or "medmad"), true_ev (int64: the row of Batch.events() under the row's first sample); med2, mad4 [n_reads] (int32), over the
+        whole read or with trim over its insert; det_off (numpy, [n_reads+1]) and n_rows from the plan.
+        outputs: the names wanted (default all); the others are None."""
+        import torch
+        c = self._detect_cfg(cfg, norm, trim)
+        want = _want(outputs, DETECT_OUTPUTS, "detect")
+        off, nr = self._detect_plan(c)                      # (validates all of cfg, and that the batch has been run)
+        dev = torch.device("cuda", self.gen.device)
+        dts = dict(dt_read=torch.int32, dt_start=torch.int64, dt_len=torch.int32, sum=torch.int64, sumsq=torch.int64, vmin=torch.int16, vmax=torch.int16,
+                   mean=torch.float32, sd=torch.float32, true_ev=torch.int64, med2=torch.int32, mad4=torch.int32)
+        dt = Chunks(n_rows=nr, det_off=off, **{n: (torch.zeros(self.n_reads if n in ("med2", "mad4") else nr, dtype=dts[n], device=dev) if n in want else None)
+                                                for n in DETECT_OUTPUTS})
+        out = _ptrs(CDetectOut, (getattr(dt, n) for n in DETECT_OUTPUTS))
+        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
+        self.gen._chk(self.gen.L.sqg_batch_detect(self.gen.ctx, self.handle, C.byref(c), C.byref(out)), "sqg_batch_detect")
+        return dt
 
     def pileup(self, p: Pileup, origin=None):
         """Adds the batch's events to the pileup `p` of SignalGenerator.new_pileup() (sqg_batch_pileup, include/sqg_pileup.h) and returns

@@ -131,6 +131,15 @@ struct PileupScratch {
     void release() { *this = PileupScratch(); }
 };
 
+// device scratch of sqg_detect_plan and sqg_batch_detect (h_detect.h): the plan, and the columns the row pass needs when the caller did not ask for them
+struct DetectScratch {
+    DevBuf<int> d_count; std::vector<int> h_count;             // [n_reads] rows of every read (k_detect_walk<false>)
+    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first row of every read, device and host
+    DevBuf<long long> d_start;                                 // [n_rows] first stored sample of every row within its read (k_detect_walk<true>)
+    DevBuf<int> d_read;                                        // [n_rows] row -> read
+    void release() { *this = DetectScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -269,6 +278,7 @@ struct sqg_ctx {
     SiteScratch site;                                          // sqg_site_plan, sqg_batch_sites (h_sites.h)
     EventScratch event;                                        // sqg_batch_events (h_events_table.h)
     PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
+    DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };
