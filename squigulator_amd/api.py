@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h and include/sqg_detect.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h and include/sqg_align.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -188,6 +188,25 @@ class CDetectOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in DETECT_OUTPUTS]
 
 
+# include/sqg_align.h: bound the same way
+EXPORTS_ALIGN = ("sqg_batch_align",)
+ALIGN_OUTPUTS = ("al_ev", "al_cost", "al_edge")
+ALIGN_DEFAULT = (4096, 4096, 65536)                         # SQG_ALIGN_DEFAULT
+ALIGN_BAND = 64
+
+
+class CAlignCfg(C.Structure):
+    _fields_ = [("stay_pen", C.c_int32), ("skip_pen", C.c_int32), ("cost_cap", C.c_int32)]
+
+
+class CAlignIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("sum", "len")]
+
+
+class CAlignOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ALIGN_OUTPUTS]
+
+
 class Pileup:
     """What SignalGenerator.new_pileup() returns: the cfg of a pileup and its sums, torch tensors [planes, hi - lo] on the context's device
     that Batch.pileup() adds to (include/sqg_pileup.h says what they hold); those not asked for are None"""
@@ -214,6 +233,7 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_EVENTS, {"sqg_batch_events": (CEventCfg, CEventOut)}),
     (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
     (EXPORTS_DETECT, {"sqg_detect_plan": (CDetectCfg,) + _PLAN, "sqg_batch_detect": (CDetectCfg, CDetectOut)}),
+    (EXPORTS_ALIGN, {"sqg_batch_align": (CAlignCfg, C.c_int64, CAlignIn, CAlignOut)}),
 )
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
@@ -240,6 +260,9 @@ def _want(outputs, names, who):
     if want - set(names):
         raise SqgError(-1, who, f"unknown outputs {sorted(want - set(names))}")
     return want
+
+
+_len = len                  # (Batch.align() takes the header's name `len` as a parameter)
 
 
 def _ptrs(struct, tensors):
@@ -788,6 +811,40 @@ class Batch:
         torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
         self.gen._chk(self.gen.L.sqg_batch_detect(self.gen.ctx, self.handle, C.byref(c), C.byref(out)), "sqg_batch_detect")
         return dt
+
+    def align(self, row_off, sum, len, cfg=None, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
+        """The rows [row_off[r], row_off[r+1]) of sum / len -- Batch.detect()'s det_off, sum and dt_len, or any other segmentation of the
+        reads -- aligned to the true events of read r by a banded dynamic programme in exact integers, on the device (sqg_batch_align,
+        include/sqg_align.h).  row_off: [n_reads+1] integers on the host; sum (int64) and len (int32): torch tensors of row_off[-1]
+        elements on the context's device.  cfg: (stay_pen, skip_pen, cost_cap), default SQG_ALIGN_DEFAULT.  torch tensors al_ev
+        [n_rows] (int64: the row of Batch.events() a row is aligned to, -1: none), al_cost [n_reads] (int64: the cost of the read's best
+        path, -1: none), al_edge [n_reads] (int32: rows on the moving band's rim).  outputs: the names wanted (default all); the others
+        are None."""
+        import torch
+        _need(self.gen.L, "sqg_batch_align", "sqg_align.h", "align")
+        three = ALIGN_DEFAULT if cfg is None else cfg
+        if isinstance(three, str) or _len(three) != 3:
+            raise SqgError(-1, "align", f"cfg must be (stay_pen, skip_pen, cost_cap), not {cfg!r}")
+        c = CAlignCfg(*(int(v) for v in three))
+        want = _want(outputs, ALIGN_OUTPUTS, "align")
+        off = np.ascontiguousarray(row_off, np.int64)
+        if off.shape != (self.n_reads + 1,):
+            raise SqgError(-1, "align", f"row_off must have {self.n_reads + 1} elements")
+        nr = max(int(off[-1]), 0)
+        dev = torch.device("cuda", self.gen.device)
+        for name, t, dt in (("sum", sum, torch.int64), ("len", len, torch.int32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
+                raise SqgError(-1, "align", f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
+        keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
+        cin = CAlignIn(sum.data_ptr() if sum.numel() else keep.data_ptr(), len.data_ptr() if len.numel() else keep.data_ptr())
+        dts = dict(al_ev=torch.int64, al_cost=torch.int64, al_edge=torch.int32)
+        al = Chunks(n_rows=nr, row_off=off, **{n: (torch.zeros(nr if n == "al_ev" else self.n_reads, dtype=dts[n], device=dev) if n in want else None)
+                                                for n in ALIGN_OUTPUTS})
+        out = _ptrs(CAlignOut, (getattr(al, n) for n in ALIGN_OUTPUTS))
+        torch.cuda.synchronize(dev)                         # (the zero fills and the caller's own work on the rows, before another stream reads them)
+        self.gen._chk(self.gen.L.sqg_batch_align(self.gen.ctx, self.handle, C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin), C.byref(out)),
+                      "sqg_batch_align")
+        return al
 
     def pileup(self, p: Pileup, origin=None):
         """Adds the batch's events to the pileup `p` of SignalGenerator.new_pileup() (sqg_batch_pileup, include/sqg_pileup.h) and returns

@@ -1,0 +1,60 @@
+// h_align.h -- sqg_batch_align: banded alignment of the caller's event rows to the true events of their reads, left on the device
+// Host side of include/sqg_align.h; included by sqg_hip.hip behind h_detect.h.  The opening of the checks, the batch's view and the
+// lifetime rule are h_chunks.h's, the scan pass and its parameters h_events_table.h's.
+#pragma once
+
+extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, const int64_t* row_off,
+                               const sqg_align_in_t* in, const sqg_align_out_t* out) {
+    static const char who[] = "sqg_batch_align";
+    int rc = check_open(c, b, cfg, "cfg", who);
+    if (rc) return rc;
+    const Check K{c, who};
+    if ((rc = K.null(row_off, "row_off")) || (rc = K.null(in, "in")) || (rc = K.null(in->sum, "in->sum")) || (rc = K.null(in->len, "in->len")) ||
+        (rc = K.null(out, "out"))) return rc;
+    if (cfg->stay_pen < 0 || cfg->stay_pen > (1 << 24)) return K.bad("stay_pen must be in 0 .. 1<<24");
+    if (cfg->skip_pen < 0 || cfg->skip_pen > (1 << 24)) return K.bad("skip_pen must be in 0 .. 1<<24");
+    if (cfg->cost_cap < 1 || cfg->cost_cap > (1 << 24)) return K.bad("cost_cap must be in 1 .. 1<<24");
+    const int n = b->n;
+    if (row_off[0] != 0) return K.bad("row_off must start at 0");
+    for (int i = 0; i < n; i++) {
+        if (row_off[i + 1] < row_off[i]) return K.bad("row_off must not decrease");
+        if (row_off[i + 1] - row_off[i] > 0x7fffffffLL) return K.bad("row_off: a read has 2^31 rows or more");
+    }
+    if ((rc = K.ran(b))) return rc;
+    if ((rc = chunk_owned(c, b, who, c->use_dwell_stream)) || n == 0) return rc;
+    const bool want_trace = out->al_ev || out->al_edge;
+    if (!want_trace && !out->al_cost) return SQG_OK;
+    AlignScratch& X = c->align;
+    const long long n_rows = (long long)row_off[n];
+    if ((rc = X.d_off.need(c, (size_t)n + 1)) || (rc = X.d_end.need(c, (size_t)n)) || (rc = X.d_level.need(c, (size_t)std::max<long long>(b->n_events, 1)))) return rc;
+    if (want_trace && ((rc = X.d_mask.need(c, (size_t)std::max<long long>(n_rows, 1))) || (rc = X.d_lo.need(c, (size_t)std::max<long long>(n_rows, 1))))) return rc;
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(X.d_off.p, row_off, ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    AlignParams P{};
+    P.bv = batch_view(c, b);
+    P.row_off = X.d_off.p; P.sum = (const long long*)in->sum; P.len = in->len; P.level_raw = X.d_level.p;
+    P.stay_pen = cfg->stay_pen; P.skip_pen = cfg->skip_pen; P.cost_cap = cfg->cost_cap;
+    P.tr_mask = X.d_mask.p; P.tr_lo = X.d_lo.p; P.end_j = X.d_end.p;
+    P.al_ev = (long long*)out->al_ev; P.al_cost = (long long*)out->al_cost; P.al_edge = out->al_edge;
+    // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone)
+    if (b->n_events > 0) {
+        EventParams Q{P.bv, (const float2*)nullptr, b->n_events};
+        Q.level_raw = X.d_level.p;
+        hipLaunchKernelGGL(k_evtab_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = dbg_sync(c, "k_evtab_scan"))) return rc;
+    }
+    // the forward pass: every read's band row by row, its end, and the trace when a path is wanted
+    if (want_trace) hipLaunchKernelGGL(k_align_forward<true>, dim3((unsigned)n), dim3(64), 0, st, P);
+    else hipLaunchKernelGGL(k_align_forward<false>, dim3((unsigned)n), dim3(64), 0, st, P);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = dbg_sync(c, "k_align_forward"))) return rc;
+    // the traceback
+    if (want_trace) {
+        hipLaunchKernelGGL(k_align_trace, dim3((unsigned)n), dim3(64), 0, st, P);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = dbg_sync(c, "k_align_trace"))) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SQG_OK;
+}

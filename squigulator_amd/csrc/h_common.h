@@ -140,6 +140,15 @@ struct DetectScratch {
     void release() { *this = DetectScratch(); }
 };
 
+// device scratch of sqg_batch_align (h_align.h): the row offsets, the targets' levels, the trace of the forward pass and every read's end
+struct AlignScratch {
+    DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
+    DevBuf<int16_t> d_level;                                   // [n_events] level_raw of every event (k_evtab_scan)
+    DevBuf<ulonglong2> d_mask; DevBuf<int> d_lo;               // [n_rows] the two move-code bits of every band cell, the band's first target
+    DevBuf<int> d_end;                                         // [n_reads] the target the best path ends at, -1: none
+    void release() { *this = AlignScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -279,6 +288,7 @@ struct sqg_ctx {
     EventScratch event;                                        // sqg_batch_events (h_events_table.h)
     PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
     DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
+    AlignScratch align;                                        // sqg_batch_align (h_align.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h and k_detect.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h and k_align.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -23,6 +23,8 @@
 //   k_pileup      the same events added across reads into per-key integer sums the caller keeps: scatter-accumulate by no-return integer atomics (include/sqg_pileup.h)
 //   k_detect_*    the two-window t-statistic event detector on the stored signal, one read per lane from LDS tiles of 64 reads, then the detected rows'
 //                 sums by k_evtab's reduction and the true event under each row's first sample (include/sqg_detect.h)
+//   k_align_*     the caller's event rows aligned to the read's true events: a banded dynamic programme, one wavefront per read and one band cell per lane,
+//                 the move codes as lane masks, then the traceback over tiles of 64 trace rows (include/sqg_align.h)
 //   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
@@ -52,3 +54,4 @@
 #include "k_events_table.h"
 #include "k_pileup.h"
 #include "k_detect.h"
+#include "k_align.h"
