@@ -746,3 +746,80 @@ size_t orc_svb_zd(const int16_t *sig, int64_t n, uint8_t *out) {
     if (count & 3) *key = kb;                                        /* the last, partial key byte */
     return (size_t)(data - out);
 }
+
+/* ------------------------------------------------------------------ */
+/* banded alignment of event rows (include/sqg_align.h), for the tests  */
+/* ------------------------------------------------------------------ */
+
+/* The rule of include/sqg_align.h for one read, cell by cell in 64-bit integers: tests/align_ref.py's banded() states it in numpy,
+ * one call per row, and tests/test_align.py holds this statement to that one bit for bit.  q [m]: the rows' values
+ * floor(256 sum / max(len, 1)), each below 2^61 in magnitude; lv [T]: the targets' levels 256 * level_raw in stored-sample order.
+ * js [m]: the target of every row, or -1; *cost, *edge as al_cost and al_edge.  Returns 0, or -1 without memory. */
+#define ORC_ALIGN_BAND 64
+#define ORC_ALIGN_INF ((int64_t)1 << 62)
+int orc_align_banded(const int64_t *q, int64_t m, const int64_t *lv, int64_t T, int64_t stay_pen, int64_t skip_pen, int64_t cost_cap,
+                     int64_t *js, int64_t *cost, int32_t *edge) {
+    *cost = -1;
+    *edge = 0;
+    if (m <= 0) return 0;
+    for (int64_t i = 0; i < m; i++) js[i] = -1;
+    if (T <= 0) return 0;
+    int64_t *los = (int64_t *)malloc((size_t)m * sizeof *los);
+    uint8_t *codes = (uint8_t *)malloc((size_t)m * ORC_ALIGN_BAND);
+    if (!los || !codes) { free(los); free(codes); return -1; }
+    int64_t prev[ORC_ALIGN_BAND], cur[ORC_ALIGN_BAND];
+    int64_t lo = 0, prev_lo = 0;
+    for (int64_t i = 0; i < m; i++) {
+        uint8_t *code = codes + (size_t)i * ORC_ALIGN_BAND;
+        for (int l = 0; l < ORC_ALIGN_BAND; l++) {
+            const int64_t j = lo + l;
+            cur[l] = ORC_ALIGN_INF;
+            code[l] = 3;
+            if (j >= T) continue;
+            int64_t c = q[i] - lv[j];
+            if (c < 0) c = -c;
+            if (c > cost_cap) c = cost_cap;
+            if (i == 0) { cur[l] = c + j * skip_pen; continue; }
+            /* the cell's three predecessors in the row before, INF outside its band; the FIRST of the smallest: step, stay, skip */
+            const int64_t k = j - prev_lo;
+            int64_t best = k - 1 >= 0 && k - 1 < ORC_ALIGN_BAND ? prev[k - 1] : ORC_ALIGN_INF;
+            int mv = 0;
+            const int64_t stay = (k >= 0 && k < ORC_ALIGN_BAND ? prev[k] : ORC_ALIGN_INF) + stay_pen;
+            const int64_t skip = (k - 2 >= 0 && k - 2 < ORC_ALIGN_BAND ? prev[k - 2] : ORC_ALIGN_INF) + skip_pen;
+            if (stay < best) { best = stay; mv = 1; }
+            if (skip < best) { best = skip; mv = 2; }
+            if (best >= ORC_ALIGN_INF) continue;
+            cur[l] = best + c;
+            code[l] = (uint8_t)mv;
+        }
+        los[i] = lo;
+        int a = 0;                                          /* the lowest target of the smallest cell; lo if the whole row is INF */
+        for (int l = 1; l < ORC_ALIGN_BAND; l++) if (cur[l] < cur[a]) a = l;
+        memcpy(prev, cur, sizeof prev);
+        prev_lo = lo;
+        const int64_t shift = a - 31;
+        lo += shift < 0 ? 0 : shift > 2 ? 2 : shift;
+    }
+    lo = prev_lo;
+    int64_t end = -1, best = 0;
+    for (int l = 0; l < ORC_ALIGN_BAND; l++) {
+        if (prev[l] >= ORC_ALIGN_INF) continue;
+        const int64_t v = prev[l] + (T - 1 - (lo + l)) * skip_pen;
+        if (end < 0 || v < best) { best = v; end = lo + l; }
+    }
+    if (end >= 0) {
+        static const int step[4] = {1, 0, 2, 0};
+        int64_t j = end;
+        int32_t rim = 0;
+        for (int64_t i = m - 1; i >= 0; i--) {
+            js[i] = j;
+            rim += j == los[i] + ORC_ALIGN_BAND - 1 || (j == los[i] && los[i] > 0);
+            j -= step[codes[(size_t)i * ORC_ALIGN_BAND + (size_t)(j - los[i])]];
+        }
+        *cost = best;
+        *edge = rim;
+    }
+    free(los);
+    free(codes);
+    return 0;
+}

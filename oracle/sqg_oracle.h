@@ -192,6 +192,11 @@ size_t   orc_svb_zd(const int16_t *sig, int64_t n_samples, uint8_t *out);
 /* worker id of read i in a batch of n_rec under -t T (src/thread.c:80-99,122-125) */
 int32_t  orc_worker_of(int32_t i, int32_t n_rec, int32_t T);
 
+/* ---- the banded alignment of include/sqg_align.h for one read, in plain C: a fast second statement of tests/align_ref.py's
+ * banded(), held to it bit for bit by tests/test_align.py.  q [m] row values (|q| < 2^61), lv [T] levels; js [m], *cost, *edge out. */
+int      orc_align_banded(const int64_t *q, int64_t m, const int64_t *lv, int64_t T, int64_t stay_pen, int64_t skip_pen, int64_t cost_cap,
+                          int64_t *js, int64_t *cost, int32_t *edge);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ SEED = 42
 GEOMETRIES = {
     "exact1": ("dna-r9-prom", profiles.SQ_IDEAL_TIME, 1.0, 0.0),       # n = bases - k + 1
     "exact2": ("dna-r9-prom", profiles.SQ_IDEAL_TIME, 2.0, 0.0),       # n = 2 (bases - k + 1): always even
+    "exact15": ("dna-r9-prom", profiles.SQ_IDEAL_TIME, 15.0, 0.0),     # n = 15 (bases - k + 1): few events under many samples, reads that start at odd samples too
     "drawn": ("dna-r9-prom", 0, None, None),                           # ordinary dwells (9 +- 4): the labels' event boundaries are irregular
 }
 

@@ -110,6 +110,8 @@ def lib():
         L.orc_svb_zd_bound.argtypes = [C.c_int64]
         L.orc_svb_zd.restype = C.c_size_t
         L.orc_svb_zd.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.orc_align_banded.restype = C.c_int
+        L.orc_align_banded.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -229,6 +231,21 @@ def svb_zd(sig):
     out = np.zeros(L.orc_svb_zd_bound(len(sig)), np.uint8)
     n = L.orc_svb_zd(sig.ctypes.data, len(sig), out.ctypes.data)
     return out[:n].copy()
+
+
+def align_banded(q, Lv, cfg):
+    """align_ref.banded(q, Lv, cfg) by the oracle's plain C statement of the same rule (oracle/sqg_oracle.c): -> (js, cost, edge).
+    A q that 64-bit differences cannot hold goes to align_ref itself"""
+    import numpy as np
+    if any(abs(int(v)) >= 1 << 61 for v in q):
+        import align_ref
+        return align_ref.banded(q, Lv, cfg)
+    qa, la = np.array(q, np.int64).reshape(len(q)), np.array(Lv, np.int64).reshape(len(Lv))
+    js = np.zeros(len(qa), np.int64)
+    cost, edge = C.c_int64(), C.c_int32()
+    rc = lib().orc_align_banded(qa.ctypes.data, len(qa), la.ctypes.data, len(la), int(cfg[0]), int(cfg[1]), int(cfg[2]), js.ctypes.data, C.byref(cost), C.byref(edge))
+    assert rc == 0
+    return js, int(cost.value), int(edge.value)
 
 
 def svb_zd_decode(enc):

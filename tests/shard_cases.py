@@ -3,8 +3,12 @@
 worker[] array) -- and what the consumer calls of include/sqg_*.h must produce on them: the numpy references of the single-context test
 files, fed with the reads of the oracle's single-process run that a rank holds.  Not collected."""
 import numpy as np
+import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
 
+import align_ref as AL
 import chunks_ref as R
+import detect_ref as DT
+import detect_vec as DVEC
 import events_ref as EV
 import events_vec as VEC
 import orc
@@ -21,6 +25,10 @@ CHUNK = (512, 256, 128)                                     # chunk_len, stride,
 CHUNK_SETTINGS = (("f16", "medmad"), ("f32", "pa"))
 SITE_GEOMETRIES = ((256, 128), (64, 32))                    # (win_len, before); the focus is (k + 1) // 2
 EVENT_SETTINGS = (("pa", False), ("medmad", False), ("pa", True), ("medmad", True))
+DETECT_B = (3, 6, 4.0, 3.0, 0.2)                            # "detect B": thresholds under which both detectors record
+ALIGN_TRUTH = (256, 1024, 16384)                            # "align truth": the cfg of tests/test_align.py
+ALIGN_DEFAULT = (4096, 4096, 65536)                         # SQG_ALIGN_DEFAULT, typed out: "align detected" passes no cfg
+EVENT_INDICES = ("true_ev", "al_ev")                        # the columns that hold batch-wide event indices: restrict() renumbers them
 KEY_BASE = (1 << 40) + 12345                                # the caller's origin of the staged jobs: keys past 32 bits
 METH_LETTERS = b"ACGTM" + b"ACGTM" + b"ACGTM" + b"mN"
 
@@ -162,6 +170,46 @@ class Setup:
         ok, key, _ = PR.eligible_and_key(ev, ev_off, o["key0"][idx], o["step"][idx], o["lens"][idx], self.k, self.rna, self.prefix)
         return key[ok]
 
+    def detect_settings(self, threaded=False):
+        """name -> (cfg, the preset's name or the cfg as Batch.detect takes it, norm, trim)"""
+        preset = "rna" if self.rna else "dna"
+        out = {"detect A": (DT.RNA if self.rna else DT.DNA, preset, "pa", False)}
+        if not threaded:
+            out["detect B"] = (DETECT_B, DETECT_B, "medmad", True)
+        return out
+
+    def expected_detect_align(self, reads, ev, threaded=False, seen=None, plain=False):
+        """the groups of sqg_batch_detect and sqg_batch_align: detect_ref and align_ref over the reads and over ev, events_ref's table of
+        them ("pa", untrimmed).  seen: a dict that gets detect_ref's info of every detect group.  The two references walk every row in
+        Python, some seconds for a job's rows, so what walks here is their second statement each -- detect_vec.batch_rows_of_reads (the
+        boundaries stay detect_ref's) and the oracle's compiled banded recurrence; plain=True takes detect_ref.batch_rows and
+        align_ref.banded themselves: tests/test_sharded_consumers.py and tests/test_align.py hold the two ways to each other bit for bit"""
+        p, k, rna, prefix, sps = self.prof, self.k, self.rna, self.prefix, self.sps
+        rows_of = DT.batch_rows if plain else DVEC.batch_rows_of_reads
+        banded = AL.banded if plain else orc.align_banded
+        out, det = {}, {}
+        for name, (cfg, _, norm, trim) in self.detect_settings(threaded).items():
+            info = {}
+            w = det[name] = rows_of(reads, cfg, k, rna, prefix, sps, norm, trim, p.range, p.digitisation, info)
+            if seen is not None:
+                seen[name] = info
+            out[name] = dict(off=w["det_off"], read=w["dt_read"], rows={key: w[key] for key in DT.PER_ROW if key != "dt_read"},
+                             per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+        w, ev_off = det["detect A"], ev["ev_off"]
+        a = AL.batch(w["det_off"], w["sum"], w["dt_len"], ev_off, ev["level_raw"], rna, ALIGN_DEFAULT, one=banded)
+        out["align detected"] = dict(off=w["det_off"], read=w["dt_read"], rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
+        if not threaded:
+            def both(q, lv, cfg):                           # a read of at most 32 events: the full matrix as well, what is compared is held to both
+                js, cost, edge = banded(q, lv, cfg)
+                if len(lv) <= 32:
+                    fj, fc, fe = AL.full(q, lv, cfg)
+                    assert fj.tolist() == js.tolist() and (fc, fe) == (cost, edge), "align_ref's two statements differ"
+                return js, cost, edge
+            idx = stored_order(ev_off, rna)
+            a = AL.batch(ev_off, ev["sum"][idx], ev["ev_len"][idx], ev_off, ev["level_raw"], rna, ALIGN_TRUTH, one=both)
+            out["align truth"] = dict(off=ev_off, read=ev["ev_read"], rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
+        return out
+
     # ---- the references, as groups: name -> dict(off [n_reads + 1], read [rows], rows {key: [rows, ...]}, per_read {key: [n_reads]})
     def expected(self, reads, threaded=False):
         p, k, rna, meth, prefix, sps, mean = self.prof, self.k, self.rna, self.meth, self.prefix, self.sps, self.mean
@@ -194,6 +242,8 @@ class Setup:
             w = EV.batch_events(reads, mean, k, rna, meth, prefix, sps, norm, trim, p.range, p.digitisation)
             out[f"events {norm} {int(trim)}"] = dict(off=w["ev_off"], read=w["ev_read"], rows={key: w[key] for key in EV.PER_EVENT if key != "ev_read"},
                                                     per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+            if (norm, trim) == EVENT_SETTINGS[0]:
+                out.update(self.expected_detect_align(reads, w, threaded))
         if prefix and not threaded:
             seg, shift = SR.batch_segments(reads, k, rna, prefix, sps)
             out["segments"] = dict(off=np.arange(n + 1, dtype=np.int64), read=np.arange(n, dtype=np.int32), rows=dict(seg=seg, shift=shift), per_read={})
@@ -260,6 +310,21 @@ class Setup:
             assert ev.n_events == b.n_events
             out[f"events {norm} {int(tr)}"] = dict(off=b.ev_off, read=cpu(ev.ev_read), rows={key: cpu(getattr(ev, key), key) for key in EV.PER_EVENT if key != "ev_read"},
                                                   per_read=dict(med2=cpu(ev.med2), mad4=cpu(ev.mad4)))
+        for name, (_, cfg, norm, tr) in self.detect_settings(threaded).items():
+            dt = b.detect(cfg, norm, tr)
+            plan, nr = b.detect_plan(cfg)
+            assert nr == dt.n_rows == len(dt.dt_read) and plan[-1] == nr
+            out[name] = dict(off=dt.det_off, plan=plan, read=cpu(dt.dt_read), rows={key: cpu(getattr(dt, key)) for key in DT.PER_ROW if key != "dt_read"},
+                             per_read=dict(med2=cpu(dt.med2), mad4=cpu(dt.mad4)))
+            if name == "detect A":                          # the tensors handed on as they are, under SQG_ALIGN_DEFAULT
+                al = b.align(dt.det_off, dt.sum, dt.dt_len)
+                assert al.n_rows == nr
+                out["align detected"] = dict(off=al.row_off, read=cpu(dt.dt_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
+        if not threaded:                                    # the true table's own rows in stored-sample order: row_off is ev_off
+            ev = b.events(outputs=("ev_read", "sum", "ev_len"))
+            idx = torch.from_numpy(stored_order(b.ev_off, self.rna)).to(ev.sum.device)
+            al = b.align(b.ev_off, ev.sum[idx].contiguous(), ev.ev_len[idx].contiguous(), ALIGN_TRUTH)
+            out["align truth"] = dict(off=al.row_off, read=cpu(ev.ev_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
         if self.prefix and not threaded:
             seg, shift = b.segments()
             out["segments"] = dict(off=np.arange(b.n_reads + 1, dtype=np.int64), read=np.arange(b.n_reads, dtype=np.int32), rows=dict(seg=cpu(seg), shift=cpu(shift)), per_read={})
@@ -272,6 +337,15 @@ class Setup:
 
 
 _ORACLE = {}                                                # (job name, flags) -> the oracle's run
+
+
+def stored_order(ev_off, rna):
+    """a batch's event indices, every read's in stored-sample order: an RNA read's events are stored last to first"""
+    idx = np.arange(int(ev_off[-1]), dtype=np.int64)
+    if rna:
+        for r in range(len(ev_off) - 1):
+            idx[int(ev_off[r]):int(ev_off[r + 1])] = idx[int(ev_off[r]):int(ev_off[r + 1])][::-1]
+    return idx
 
 
 def _host(t, key=None):
@@ -296,8 +370,12 @@ def assert_groups(got, want, what):
 
 
 def restrict(groups, idx):
-    """the groups of a whole batch restricted to the reads idx (increasing) and renumbered: what the rank that holds them must produce"""
+    """the groups of a whole batch restricted to the reads idx (increasing) and renumbered: what the rank that holds them must produce.
+    The rows' reads are renumbered, and so are the batch-wide event indices of EVENT_INDICES: the event at place j of read idx[i] of the
+    whole batch is the event at place j of read i of the rank's (-1, no event, stays)"""
     idx = np.asarray(idx, np.int64)
+    ev_whole = np.asarray(groups[f"events {EVENT_SETTINGS[0][0]} {int(EVENT_SETTINGS[0][1])}"]["off"], np.int64)
+    ev_rank = np.concatenate(([0], np.cumsum(ev_whole[idx + 1] - ev_whole[idx]))).astype(np.int64)
     out = {}
     for name, g in groups.items():
         off = np.asarray(g["off"], np.int64)
@@ -307,6 +385,11 @@ def restrict(groups, idx):
                          read=np.repeat(np.arange(len(idx)), counts).astype(g["read"].dtype),
                          rows={key: a[rows] for key, a in g["rows"].items()}, per_read={key: a[idx] for key, a in g["per_read"].items()})
         assert np.array_equal(g["read"][rows], np.repeat(idx, counts))
+        shift = np.repeat(ev_rank[:-1] - ev_whole[idx], counts)      # per row: its read's first event in the rank's numbering less that in the batch's
+        for key in EVENT_INDICES:
+            if key in out[name]["rows"]:
+                v = out[name]["rows"][key]
+                out[name]["rows"][key] = np.where(v < 0, v, v + shift).astype(v.dtype)
     return out
 
 

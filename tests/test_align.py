@@ -12,6 +12,7 @@ import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch
 
 import align_ref as A
 import inject
+import orc
 from chunk_support import _context, _declared, _fixture_reads
 from refvec_cases import REFVEC_CASES
 from squigulator_amd import api, build, model, profiles
@@ -131,6 +132,36 @@ def test_the_band_moves_with_the_path():
     assert js.tolist() == np.repeat(np.arange(300), 3).tolist() and cost == 600 * 256 and edge == 0
     js, cost, edge = A.banded(lv[2::3], lv, CFG)            # every third: a row moves two targets at the most, the path is lost.  Every
     assert js.tolist() != list(range(2, 300, 3)) and cost >= 200 * 1024      # target that no row visits is charged skip_pen, 200 at least
+
+
+def test_the_compiled_statement_is_the_banded_recurrence():
+    """orc.align_banded, the oracle's plain C statement of the rule (the sharded suite's references walk hundreds of thousands of rows
+    with it), against (a) bit for bit: the tie-heavy reads of the test above with T up to 400 and m up to 600 (the band moves), every
+    penalty at 0 and at its maximum, the hand-made paths of the band test, rows far off every target, negative and huge q, no rows and
+    no targets"""
+    rng = np.random.default_rng(5)
+
+    def same(q, lv, cfg, what):
+        a, b = A.banded(q, lv, cfg), orc.align_banded(q, lv, cfg)
+        assert a[0].tolist() == b[0].tolist() and a[1:] == b[1:] and b[0].dtype == np.int64, (what, cfg, a[1:], b[1:])
+        return a
+
+    cfgs = [CFG, api.ALIGN_DEFAULT, (0, 0, 100000), (0, 0, 1), (1 << 24, 0, 77), (0, 1 << 24, 1 << 24), (300, 300, 300), (1 << 24, 1 << 24, 1 << 24), (0, 1, 100)]
+    n_ties = n_edge = n_moved = 0
+    for trial in range(300):
+        big = trial % 3 == 0
+        T, m = int(rng.integers(0, 400 if big else 70)), int(rng.integers(0, 600 if big else 90))
+        levels, jitter = ((400, 700), 0) if trial % 2 else (np.arange(300, 900, 50), 40)
+        q, lv = _random_case(rng, T, m, levels, jitter)
+        js, cost, edge = same(q, lv, cfgs[trial % len(cfgs)], trial)
+        n_ties += int(m > 2 and T > 2 and len(set(q)) < m); n_edge += int(edge > 0); n_moved += int(len(js) > 0 and js.max() > 80)
+    assert n_ties > 100 and n_edge > 5 and n_moved > 20, (n_ties, n_edge, n_moved)
+    lv = [256 * int(v) for v in rng.permutation(np.arange(200, 3200, 10))]
+    for q in (lv, lv[1::2], np.repeat(lv, 3).tolist(), lv[2::3], [40000 * 256] * 500, [-(1 << 60), 1 << 60] * 40, [5] * 6):
+        for cfg in cfgs:
+            same(q, lv, cfg, "made-up rows")
+    for q, t in (([], lv), ([1, 2], []), ([], []), ([7], lv[:1]), ([1 << 61, -(1 << 62), 3], lv[:40])):
+        same(q, t, CFG, "edges")
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU
@@ -372,8 +403,9 @@ def _raw(gen, b, cfg, row_off, cin, out):
 
 @pytest.mark.gpu
 def test_interface():
-    """NULL outputs and each output alone; every SQG_EINVAL of the header with its message; a batch that has not been run; an empty
-    batch; a second call gives the same bytes; nothing outside [row_off[0], row_off[n]) is written (guard values around the arrays)"""
+    """NULL outputs and each output alone; every SQG_EINVAL of the header with its message; a read of 2^31 rows; a batch that has not
+    been run; an empty batch; a second call gives the same bytes; nothing outside [row_off[0], row_off[n]) is written (guard values
+    around the arrays)"""
     gen, prof, fl, k = inject.context("exact1")
     counts = [70, 5, 300]
     seqs = inject.seqs_for([t + k - 1 for t in counts])
@@ -439,6 +471,13 @@ def test_interface():
         assert _raw(gen, b, api.CAlignCfg(**dict(good, **bad)), row_off, cin, out) == -1 and b"sqg_batch_align" in err() and what in err(), (bad, err())
     for bad_off, what in [(row_off + 1, b"start at 0"), (np.array([0, 5, 4, 9], np.int64), b"decrease"), (np.array([0, -1, 4, 9], np.int64), b"decrease")]:
         assert _raw(gen, b, cfg, bad_off, cin, out) == -1 and b"row_off" in err() and what in err(), err()
+    # a read of 2^31 rows: refused from row_off alone, before any array is read (none of that size exists)
+    before = {key: bufs[key].cpu().numpy().copy() for key in OUT}
+    assert _raw(gen, b, cfg, np.array([0, 2 ** 31, 2 ** 31, 2 ** 31], np.int64), cin, out) == -1 and b"sqg_batch_align" in err() and b"row_off" in err() and b"2^31 rows" in err(), err()
+    torch.cuda.synchronize(dev)
+    for key in OUT:                                         # guards and rows as the call before left them
+        np.testing.assert_array_equal(bufs[key].cpu().numpy(), before[key], err_msg=f"{key}: a refused row_off wrote")
+        assert (before[key][:G] == -77).all() and (before[key][-G:] == -77).all()
     assert gen.L.sqg_batch_align(None, None, None, None, None, None) == -1
     assert gen.L.sqg_batch_align(None, b.handle, C.byref(cfg), row_off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin), C.byref(out)) == -1
     assert _raw(gen, None, cfg, row_off, cin, out) == -1 and b"sqg_batch_align" in err() and b"batch" in err()

@@ -1,13 +1,15 @@
 """The calls that read a finished batch on the device share scratch of the context (the reads' constants, the inserts' spans, the chunk
-and site plans, the event columns): what a call writes must not depend on which other calls ran before it on that context.  Every call
-alone on a fresh context is the reference; the same calls in the listed order, in reverse, and across two consecutive batches -- those
-for batch 0 made after batch 1 has run, while batch 0 still owns its device results -- must give the same tensors, bit for bit."""
+and site plans, the event columns, the detector's plan, the aligner's levels): what a call writes must not depend on which other calls
+ran before it on that context.  Every call alone on a fresh context is the reference; the same calls in the listed order, in reverse,
+and across two consecutive batches -- those for batch 0 made after batch 1 has run, while batch 0 still owns its device results --
+must give the same tensors, bit for bit."""
 import numpy as np
 import pytest
 import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
 
 from chunk_support import _context, _fixture_reads
 from refvec_cases import REFVEC_CASES
+from shard_cases import stored_order
 from squigulator_amd import api
 
 L, S, W = 64, 8, 16
@@ -24,6 +26,19 @@ def _segments(b):
     return api.Chunks(seg=seg, shift=shift)
 
 
+def _align_detected(b):
+    """the detected rows of the DNA preset, the tensors handed on as they are, aligned under SQG_ALIGN_DEFAULT"""
+    dt = b.detect("dna", outputs=("sum", "dt_len"))
+    return b.align(dt.det_off, dt.sum, dt.dt_len)
+
+
+def _align_truth(b):
+    """the true table's own sum / ev_len as the rows, every read's in stored-sample order (an RNA read's events are stored last to first)"""
+    ev = b.events(outputs=("sum", "ev_len"))
+    idx = torch.from_numpy(stored_order(b.ev_off, True)).to(ev.sum.device)
+    return b.align(b.ev_off, ev.sum[idx].contiguous(), ev.ev_len[idx].contiguous(), (256, 1024, 16384))
+
+
 def _origin(b):
     """one origin per read, the second on the minus strand; the window [200, 4000) leaves events of every read outside"""
     n = b.n_reads
@@ -35,17 +50,22 @@ JOBS = {
     "r9_meth": [
         ("chunks", lambda b: b.chunks(L, S, W)),
         ("chunk_targets", lambda b: b.chunk_targets(L, S, clean=True, clean_raw=True, moves=True, kmer=True)),
+        ("detect medmad", lambda b: b.detect("dna", "medmad")),
         ("sites", lambda b: b.sites(64, ctx_len=5)),
         ("events medmad", lambda b: b.events("medmad")),
+        ("align detected", _align_detected),
         ("events pa", lambda b: b.events("pa")),
         ("pileup ref medmad", lambda b: _pileup(b, origin=_origin(b), by="ref", norm="medmad", lo=200, hi=4000)),
     ],
     # RNA, SQG_PREFIX
     "rna004_prefix": [
         ("segments", _segments),
+        ("detect medmad trim", lambda b: b.detect("rna", "medmad", True)),
         ("chunks trim", lambda b: b.chunks(L, S, W, trim=True)),
+        ("align truth", _align_truth),
         ("chunk_targets trim", lambda b: b.chunk_targets(L, S, clean=True, clean_raw=True, moves=True, kmer=True, trim=True)),
         ("events medmad trim", lambda b: b.events("medmad", trim=True)),
+        ("detect pa", lambda b: b.detect("rna")),
         ("events medmad", lambda b: b.events("medmad", trim=False)),
         ("pileup kmer trim", lambda b: _pileup(b, by="kmer", norm="medmad", trim=True)),
     ],

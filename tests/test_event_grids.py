@@ -1,9 +1,9 @@
-"""The flat event grids of k_events_table.h and k_pileup.h past their first trip, pileup keys past 32 bits, the sampler's origin on several
-contigs and both strands, and long events beside lanes that are not taken.  k_evtab_reduce and k_pileup run on at most 32 workgroups per
-compute unit and walk the events with a stride of the whole grid: a batch of more than cap = 32 * CUs * 256 events is the only one whose
-events are met on a second trip.  Every comparison is bit for bit; every precondition (the event count against cap, the dwells behind cap,
-strands, contigs, taken and skipped lanes) is asserted of the batch itself, so that a device with another number of compute units either
-meets it or fails on it."""
+"""The flat grids of k_events_table.h, k_pileup.h and k_detect.h past their first trip, pileup keys past 32 bits, the sampler's origin on
+several contigs and both strands, and long events beside lanes that are not taken.  k_evtab_reduce, k_pileup and k_detect_rows run on at
+most 32 workgroups per compute unit and walk the events (k_detect_rows: the detected rows) with a stride of the whole grid: a batch of
+more than cap = 32 * CUs * 256 of them is the only one whose events are met on a second trip.  Every comparison is bit for bit; every
+precondition (the event count against cap, the dwells behind cap, strands, contigs, taken and skipped lanes) is asserted of the batch
+itself, so that a device with another number of compute units either meets it or fails on it."""
 import os
 
 import numpy as np
@@ -11,6 +11,8 @@ import pytest
 import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
 
 import chunks_ref as R
+import detect_ref as D
+import detect_vec as DVEC
 import events_ref as EV
 import events_vec as VEC
 import inject
@@ -33,6 +35,14 @@ LANE_MAX = 64       # k_events_table.h's EVT_LANE_MAX
 # can have (8 +- 30: P(dwell > 128) = 3e-5, some 10 events behind cap on 256 compute units).
 GRID_PROFILE, GRID_K, GRID_DWELL, GRID_SEED, GRID_READS, GRID_WORKERS = "dna-r9-prom", 6, (8.0, 30.0), 7, 600, 4
 LONG_READS = 12     # the constant-dwell batch: fewer, longer reads
+
+# The batch of k_detect_rows' grid: injected samples on a constant-dwell geometry.  Under DETECT_CFG the short window is one sample, where
+# t is |x[i] - x[i-1]| (D = 0): a square wave of two samples per level with +-9 of noise has a boundary at every change of level, rows of
+# two samples, and a constant stretch is one row.
+DETECT_CFG = (1, 2, 1.0, 1.0, 0.1)
+DETECT_GEOMETRY, DETECT_DWELL, DETECT_READS = "exact15", 15, 300
+DETECT_STRETCHES = (61, 62, 63, 64, 65, 66, 67, 129, 130, 200, 300) * 6      # samples of the constant stretches behind cap, in this order
+DETECT_GAPS = (7, 60)                                                         # samples of square wave between two stretches: drawn, odd and even
 
 
 def _case(cid):
@@ -84,6 +94,53 @@ def assert_dwell_mix(dw, cap):
     assert behind.max() > 2 * LANE_MAX, f"the longest dwell behind cap is {behind.max()}"
     whole = behind[:len(behind) // 64 * 64].reshape(-1, 64)                     # (cap is a multiple of 64: these are wavefronts)
     assert cap % 64 == 0 and ((whole <= LANE_MAX).any(axis=1) & (whole > LANE_MAX).any(axis=1)).any(), "no wavefront behind cap with both kinds"
+
+
+def detect_grid_lengths(cap, n_reads, dwell, seed=1):
+    """samples per read: n_reads unequal multiples of the dwell that add up to the samples cap + cap / 8 rows of two take, and the stretches"""
+    total = 2 * (cap + cap // 8) + sum(DETECT_STRETCHES) + len(DETECT_STRETCHES) * sum(DETECT_GAPS) // 2
+    w = np.random.default_rng(seed).uniform(0.25, 1.75, n_reads)
+    events = np.floor(w / w.sum() * (total / dwell)).astype(np.int64)
+    events[-1] += -(-total // dwell) - events.sum()
+    assert events.min() >= 8 and events.sum() * dwell >= total
+    return events * dwell
+
+
+def detect_grid_signal(n, cap, seed=5):
+    """n samples: 2 cap + cap / 8 samples of square wave -- rows of two: cap + cap / 16 rows --, then, behind row cap, the constant
+    stretches, each followed by a gap of square wave of a drawn length whose phase starts anew, then square wave to the end"""
+    rng = np.random.default_rng(seed)
+    wave = lambda m: np.where((np.arange(m) // 2) & 1, 900, 500)             # noqa: E731
+    parts = [wave(2 * cap + cap // 8)]
+    for ln in DETECT_STRETCHES:
+        parts += [np.full(ln, 700), wave(int(rng.integers(DETECT_GAPS[0], DETECT_GAPS[1] + 1)))]
+    used = sum(len(p) for p in parts)
+    assert used < n, (used, n)
+    x = np.concatenate(parts + [wave(n - used)])
+    flat = np.concatenate([np.zeros(len(p), bool) if i % 2 == 0 else np.ones(len(p), bool) for i, p in enumerate(parts + [x[:0]])] + [np.zeros(n - used, bool)])
+    return np.where(flat, x, x + rng.integers(-9, 10, n)).astype(np.int16)
+
+
+def detect_grid_starts(sig, sig_off):
+    """per read the first sample of every detected row: detect_ref's peak machine"""
+    return [np.array([0] + D.boundaries(sig[sig_off[r]:sig_off[r + 1]], DETECT_CFG), np.int64) for r in range(len(sig_off) - 1)]
+
+
+def assert_detect_mix(want, sig_off, cap):
+    """of the reference's rows alone: more than cap of them, the last wavefront partly empty, a read boundary inside the second trip, and
+    behind cap rows of 2, 63, 64, 65 and more than 128 samples, a group of 64 rows that holds both ways of evtab_take, and rows of either
+    way that start at odd and at even samples of the slab"""
+    n, ln = int(want["det_off"][-1]), want["dt_len"].astype(np.int64)
+    assert n > cap and n % 64 != 0 and cap % 64 == 0, (n, cap)
+    inner = want["det_off"][1:-1]
+    assert ((inner > cap) & (inner < n)).any(), "no read boundary behind cap"
+    behind = ln[cap:]
+    assert {2, LANE_MAX - 1, LANE_MAX, LANE_MAX + 1} <= set(behind.tolist()) and behind.max() > 2 * LANE_MAX, sorted(set(behind.tolist()))
+    whole = behind[:len(behind) // 64 * 64].reshape(-1, 64)
+    assert ((whole <= LANE_MAX).any(axis=1) & (whole > LANE_MAX).any(axis=1)).any(), "no group of 64 rows behind cap with both kinds"
+    at = (np.asarray(sig_off, np.int64)[want["dt_read"]] + want["dt_start"])[cap:]
+    for kind in (behind <= LANE_MAX, behind > LANE_MAX):
+        assert set((at[kind] & 1).tolist()) == {0, 1}, "rows behind cap start at samples of one parity only"
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU
@@ -142,6 +199,27 @@ def test_the_grid_batch_plan():
     assert_dwell_mix(np.array([1] * 64 + [63, 64, 65, 129] + [2] * 60 + [7] * 5), 64)
 
 
+@pytest.mark.parametrize("norm", ["pa", "medmad"])
+def test_the_vectorised_detected_rows_are_detect_ref_bit_for_bit(norm):
+    """detect_vec.batch_rows against detect_ref.batch_rows on a small batch made as the grid's: the same wave, stretches and geometry
+    with a cap of 2048 rows, so the rows are of the same kinds (assert_detect_mix); every column, the statistics and det_off"""
+    cap, k = 2048, 6
+    prof, _ = profiles.get_profile("dna-r9-prom")
+    lens = detect_grid_lengths(cap, 9, DETECT_DWELL)
+    sig_off = _offsets(lens)
+    sig = detect_grid_signal(int(sig_off[-1]), cap)
+    offset = np.random.default_rng(2).uniform(-250, 50, len(lens))
+    reads = [dict(sig=sig[sig_off[r]:sig_off[r + 1]], ss=np.full(n // DETECT_DWELL, DETECT_DWELL, np.int64), seq=b"A" * (n // DETECT_DWELL + k - 1), offset=float(offset[r]))
+             for r, n in enumerate(lens)]
+    want = D.batch_rows(reads, DETECT_CFG, k, False, False, DETECT_DWELL, norm, False, prof.range, prof.digitisation)
+    dw = np.concatenate([r["ss"] for r in reads])
+    got = DVEC.batch_rows(sig, sig_off, detect_grid_starts(sig, sig_off), dw, _offsets([len(r["ss"]) for r in reads]), offset, norm, prof.range, prof.digitisation)
+    np.testing.assert_array_equal(got["det_off"], want["det_off"])
+    _assert_same(got, want, D.PER_ROW + (D.PER_READ if norm != "pa" else ()), f"detected rows {norm}")
+    assert_detect_mix(want, sig_off, cap)
+    assert len(set(want["true_ev"].tolist())) > len(dw) // 2
+
+
 # ---------------------------------------------------------------------------------------------------------- GPU
 def _cpu(t):
     return None if t is None else t.cpu().numpy()
@@ -196,6 +274,35 @@ class _Grid:
         return d["rows"][norm]
 
 
+class _DetectGrid:
+    """one injected batch of DETECT_READS reads whose detected table under DETECT_CFG has cap * 1.13 rows, and the reference's rows of it"""
+    made = None
+
+    @classmethod
+    def get(cls):
+        if cls.made is None:
+            cap = _device_cap()
+            gen, prof, fl, k = inject.context(DETECT_GEOMETRY)
+            lens = detect_grid_lengths(cap, DETECT_READS, DETECT_DWELL)
+            b = inject.run_geometry(gen, inject.seqs_for(inject.bases_for(lens, k, DETECT_DWELL)))
+            np.testing.assert_array_equal(np.diff(b.sig_off), lens)
+            sig = detect_grid_signal(b.n_samples, cap)
+            inject.inject(b, sig)
+            dw = b.dwell()
+            assert (dw == DETECT_DWELL).all() and len(set(lens.tolist())) > DETECT_READS // 2 and lens.max() > 3 * lens.min()
+            cls.made = dict(gen=gen, b=b, cap=cap, prof=prof, sig=sig, dw=dw, starts=detect_grid_starts(sig, b.sig_off), rows={})
+        return cls.made
+
+    @classmethod
+    def rows(cls, norm):
+        d = cls.get()
+        if norm not in d["rows"]:
+            b, prof = d["b"], d["prof"]
+            d["rows"][norm] = DVEC.batch_rows(d["sig"], b.sig_off, d["starts"], d["dw"], b.ev_off, b.offset, norm, prof.range, prof.digitisation,
+                                              reuse=next(iter(d["rows"].values()), None))
+        return d["rows"][norm]
+
+
 def _assert_rows_behind_cap(got, want, keys, cap, n, what):
     """rows [cap, n) are compared, on their own, and hold something: Batch.events() hands the library zeroed arrays (fill value 0)"""
     assert cap < n
@@ -243,6 +350,34 @@ def test_events_behind_the_first_trip_of_the_grid(norm):
             np.testing.assert_array_equal(R.bits(got[key][rows]), R.bits(w[key].astype(EV.DTYPES[key])), err_msg=f"grid {norm} read {r}: {key}")
         if norm == "medmad":
             assert (int(got["med2"][r]), int(got["mad4"][r])) == (w["med2"], w["mad4"]) == R.stats(own["sig"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("norm", ["pa", "medmad"])
+def test_detected_rows_behind_the_first_trip_of_the_grid(norm):
+    """k_detect.h:184, `base += gridDim.x * CHUNK_WG` of k_detect_rows: its second trip, which no earlier test takes (their tables hold a
+    few hundred thousand rows, one trip covers 32 * CUs * 256).  Behind cap the table has rows of 2, 63, 64, 65 and more than 128
+    samples that start at odd and at even samples of the slab, and a wavefront with both kinds, so evtab_take's lane loop and its
+    ballot / shuffle loop both run there; the last wavefront is partly empty, and `if (!have) continue` at line 190 is met on the second
+    trip.  det_off of the plan call and all twelve outputs against detect_vec, which the test above pins to detect_ref"""
+    d = _DetectGrid.get()
+    b, cap = d["b"], d["cap"]
+    want = _DetectGrid.rows(norm)
+    n = int(want["det_off"][-1])
+    assert_detect_mix(want, b.sig_off, cap)
+    assert cap + cap // 16 <= n <= cap + cap // 4, (n, cap)
+    plan, n_rows = b.detect_plan(DETECT_CFG)
+    np.testing.assert_array_equal(plan, want["det_off"], err_msg="the plan")
+    dt = b.detect(DETECT_CFG, norm, False)
+    assert n_rows == dt.n_rows == n
+    np.testing.assert_array_equal(dt.det_off, want["det_off"])
+    got = _table_of(dt, api.DETECT_OUTPUTS)
+    _assert_rows_behind_cap(got, want, D.PER_ROW, cap, n, f"detect grid {norm}")
+    assert (got["dt_len"][cap:] > 0).all() and (got["sumsq"][cap:] > 0).all()
+    stats = np.array([VEC.stats_fast(d["sig"][b.sig_off[r]:b.sig_off[r + 1]]) for r in range(b.n_reads)], np.int32)      # (the whole reads' under either norm)
+    np.testing.assert_array_equal(got["med2"], stats[:, 0]); np.testing.assert_array_equal(got["mad4"], stats[:, 1])
+    if norm == "medmad":
+        np.testing.assert_array_equal(want["med2"], stats[:, 0]); np.testing.assert_array_equal(want["mad4"], stats[:, 1])
 
 
 @pytest.mark.gpu

@@ -1,9 +1,10 @@
 """The consumer calls -- sqg_batch_chunks / sqg_chunk_plan, sqg_batch_chunk_targets, sqg_batch_segments and the *_trimmed calls,
-sqg_site_plan / sqg_batch_sites, sqg_batch_events, sqg_batch_pileup -- on batches made the way several GPUs make them: range-sharded
-contexts (sqg_batch_run_begin / _end), worker-sharded contexts, and contexts on host threads of their own (tests/shard_cases.py has the
-jobs and the drivers).  What a rank that holds reads idx of the job must produce is the numpy reference of the call's header over
-[reads[i] for i in idx], the reads being those of the oracle's single-process run of the whole job; and the same job on one plain
-context, restricted to the rank's reads and renumbered, gives the same rows.  Every comparison is bit for bit (floats as integers)."""
+sqg_site_plan / sqg_batch_sites, sqg_batch_events, sqg_batch_pileup, sqg_detect_plan / sqg_batch_detect, sqg_batch_align -- on batches
+made the way several GPUs make them: range-sharded contexts (sqg_batch_run_begin / _end), worker-sharded contexts, and contexts on host
+threads of their own (tests/shard_cases.py has the jobs and the drivers).  What a rank that holds reads idx of the job must produce is
+the numpy reference of the call's header over [reads[i] for i in idx], the reads being those of the oracle's single-process run of the
+whole job; and the same job on one plain context, restricted to the rank's reads and renumbered, gives the same rows.  Every comparison
+is bit for bit (floats as integers)."""
 import ctypes as C
 import threading
 import time
@@ -11,8 +12,10 @@ import warnings
 
 import numpy as np
 import pytest
+import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
 
 import chunks_ref as R
+import events_ref as EV
 import pileup_ref as PR
 import segments_ref as SR
 import shard_cases as SC
@@ -25,13 +28,42 @@ OUT = api.PILEUP_OUTPUTS
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU
+def _detect_align_hold(su, reads, what):
+    """what the detect and align groups need of a rank's reads, asserted of detect_ref, align_ref and events_ref alone -> the detected
+    rows under either setting.  Both settings detect rows; under setting B both detectors record; the alignment of the detected rows is
+    neither the detector's own answer nor lost (true_ev is the event under a row's first sample, al_ev the event the row is aligned to);
+    RNA with a prefix has a read whose path runs along the band's rim; the staged range jobs hold a read that the full matrix covers"""
+    p = su.prof
+    ev = EV.batch_events(reads, su.mean, su.k, su.rna, su.meth, su.prefix, su.sps, "pa", False, p.range, p.digitisation)
+    seen = {}
+    w = su.expected_detect_align(reads, ev, seen=seen)
+    rows = {name: len(w[name]["read"]) for name in ("detect A", "detect B")}
+    assert min(rows.values()) > len(reads), f"{what}: detected rows {rows}"
+    assert seen["detect B"]["short"] >= 1 and seen["detect B"]["long"] >= 1, f"{what}: under setting B the detectors recorded {seen['detect B']}"
+    assert np.array_equal(w["align detected"]["off"], w["detect A"]["off"]) and np.array_equal(w["align truth"]["off"], ev["ev_off"])
+    share = float((w["align detected"]["rows"]["al_ev"] == w["detect A"]["rows"]["true_ev"]).mean())
+    edge = int((w["align detected"]["per_read"]["al_edge"] > 0).sum())
+    few = int((np.diff(ev["ev_off"]) <= 32).sum())
+    print(f"{what}: {share:.3f} of the detected rows aligned to the event under their first sample, {edge} reads with al_edge > 0, {few} reads of at most 32 events")
+    assert 0.5 < share < 1, f"{what}: {share} of the detected rows are aligned to the event under their first sample"
+    if su.name == "rna004_prefix_g2":
+        assert edge > 0, f"{what}: no read with al_edge > 0"
+    if "short" in su.job:
+        assert few > 0, f"{what}: no read of at most 32 events"
+        short = [i for i, r in enumerate(reads) if len(r["seq"]) < su.k]            # these are among them: five stand-in events each
+        print(f"{what}: the reads shorter than a k-mer have {[int(w['detect A']['off'][i + 1] - w['detect A']['off'][i]) for i in short]} detected rows")
+        assert short and all(ev["ev_off"][i + 1] - ev["ev_off"][i] == 5 for i in short)
+    return rows
+
+
 @pytest.mark.parametrize("name", SHARDED)
 def test_the_jobs_hold_what_can_go_wrong(name):
     """from the oracle and the numpy references alone: every rank but the designated empty one holds a read; a sampled DNA job holds both
     strands; a job with sites holds a site in every rank that has a read, a dropped candidate and under SQG_METH both labels; a job
     piled up by position has a key that reads of two different ranks add to; a staged job's steps take all three values in every rank;
-    every rank of the staged range jobs holds a read shorter than a k-mer, as its first or last read among others; and the chunk, site and
-    event counts of a batch's ranks are above zero and differ from rank to rank"""
+    every rank of the staged range jobs holds a read shorter than a k-mer, as its first or last read among others; the chunk, site,
+    event and detected-row counts of a batch's ranks are above zero and differ from rank to rank; and every rank that holds a read holds
+    what the detect and align groups need (_detect_align_hold)"""
     su = SC.Setup(name)
     j = su.job
     job = su.oracle_job()
@@ -54,6 +86,8 @@ def test_the_jobs_hold_what_can_go_wrong(name):
                 w = su.expected_sites(reads)
                 row.update(sites=int(w["site_off"][-1]), label1=int(w["label"].sum()), dropped=int(w["dropped"].sum()))
                 labels |= set(w["label"].tolist()); dropped += row["dropped"]
+            if len(idx):
+                row.update(_detect_align_hold(su, reads, f"{name} batch {bi} rank {g}"))
             if not su.sampled and len(idx):
                 assert set(o["step"][idx].tolist()) == {-1, 0, 1}, f"{name} batch {bi} rank {g}: steps {o['step'][idx]}"
             keys.append(set(su.keys(o, idx).tolist()))
@@ -64,7 +98,7 @@ def test_the_jobs_hold_what_can_go_wrong(name):
         print(f"{name} batch {bi}: strands {o['strand']}, {len(shared)} positions keyed by reads of two different ranks")
         strands |= set(o["strand"] or "")
         full = [c for c in counts if c["reads"]]
-        for what in ("events", "chunks") + (("sites",) if su.sites else ()):
+        for what in ("events", "chunks", "detect A", "detect B") + (("sites",) if su.sites else ()):
             vals = [c[what] for c in full]
             assert min(vals) > 0 and len(set(vals)) == len(vals), f"{name} batch {bi}: {what} per rank {vals}"
         if "expect" in j:                                   # the figures of the case table
@@ -91,6 +125,51 @@ def test_the_jobs_hold_what_can_go_wrong(name):
     kw = su.pile_cfgs()["ref_window"][0]
     allk = np.concatenate([su.keys(o, np.arange(len(o["reads"]))) for o in job])
     assert kw["lo"] < kw["hi"] and (allk < kw["lo"]).any() and (allk >= kw["hi"]).any()          # the window cuts reads
+
+
+@pytest.mark.parametrize("name", ["staged_t2_g2_meth", "rna004_prefix_g2", "r10_g2"])
+def test_the_fast_statements_are_the_plain_references(name):
+    """the groups as the GPU tests take them -- detect_vec.batch_rows_of_reads and the oracle's compiled banded recurrence -- against
+    detect_ref.batch_rows and align_ref.banded themselves, bit for bit, on every rank of a job's first batch: reads shorter than a k-mer
+    and SQG_METH; RNA with a prefix, trimmed statistics and paths on the band's rim; R10's nine-base k-mers"""
+    su = SC.Setup(name)
+    p = su.prof
+    o = su.oracle_job()[0]
+    for g in range(su.G):
+        reads = [o["reads"][i] for i in su.rank_reads(len(o["reads"]), g)]
+        ev = EV.batch_events(reads, su.mean, su.k, su.rna, su.meth, su.prefix, su.sps, "pa", False, p.range, p.digitisation)
+        fast, plain = {}, {}
+        SC.assert_groups(su.expected_detect_align(reads, ev, seen=fast), su.expected_detect_align(reads, ev, seen=plain, plain=True), f"{name} rank {g}")
+        assert fast == plain and fast["detect B"]["long"] >= 1
+
+
+@pytest.mark.parametrize("name", ["staged_t2_g2", "rna004_prefix_g2", "workers_t6_g3"])
+def test_restrict_renumbers_the_event_indices(name):
+    """the references alone: the detect and align groups of a whole batch, restricted to a rank's reads, are the groups of those reads --
+    true_ev and al_ev in the rank's own numbering of the events, as absolute indices; for every rank but the first they differ from the
+    whole batch's"""
+    su = SC.Setup(name)
+    p = su.prof
+    o = su.oracle_job()[0]
+    table = lambda reads: EV.batch_events(reads, su.mean, su.k, su.rna, su.meth, su.prefix, su.sps, "pa", False, p.range, p.digitisation)      # noqa: E731
+    ev = table(o["reads"])
+    whole = su.expected_detect_align(o["reads"], ev)
+    whole["events pa 0"] = dict(off=ev["ev_off"], read=ev["ev_read"], rows={}, per_read={})
+    moved = 0
+    for g in range(su.G):
+        idx = su.rank_reads(len(o["reads"]), g)
+        reads = [o["reads"][i] for i in idx]
+        evr = table(reads)
+        want = su.expected_detect_align(reads, evr)
+        want["events pa 0"] = dict(off=evr["ev_off"], read=evr["ev_read"], rows={}, per_read={})
+        got = SC.restrict(whole, idx)
+        SC.assert_groups(got, want, f"{name} rank {g}")
+        for gname, key in (("detect A", "true_ev"), ("detect B", "true_ev"), ("align detected", "al_ev"), ("align truth", "al_ev")):
+            v = got[gname]["rows"][key]
+            assert len(v) and (v >= 0).all() and (v < evr["ev_off"][-1]).all()
+            rows = np.concatenate([np.arange(whole[gname]["off"][i], whole[gname]["off"][i + 1]) for i in idx])
+            moved += int((whole[gname]["rows"][key][rows] != v).any())
+    assert moved >= 4 * (su.G - 1)
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU
@@ -127,6 +206,7 @@ def test_consumers_on_every_rank(name, mode):
             for gname, grp in out.items():
                 assert len(grp["read"]) == 0 and list(grp["off"]) == [0], gname
             assert list(out["sites 256"]["plan"]) == [0]
+            _empty_detect_and_align(b)
             for cname, call in _raw_calls(su, b).items():   # (Batch.chunks and .chunk_targets do not call the library for a plan without chunks)
                 assert call() == 0, f"{cname} on the empty range: {b.gen.L.sqg_last_error(b.gen.ctx)}"
             lo, hi = su.window()
@@ -185,6 +265,27 @@ def test_the_pileups_of_the_ranks_add_up(name, mode):
         assert tuple(stats[c]) == (one[c][1], one[c][2]) == (counted, outside)
 
 
+def _empty_detect_and_align(b):
+    """a rank without reads: no rows, det_off is [0], and outputs handed in prefilled with guard values come back as they were"""
+    dt = b.detect("dna", "medmad", True)
+    al = b.align(np.zeros(1, np.int64), dt.sum, dt.dt_len)
+    assert dt.n_rows == al.n_rows == 0 and dt.det_off.tolist() == [0] and b.detect_plan()[1] == 0
+    assert all(tuple(getattr(dt, key).shape) == (0,) for key in api.DETECT_OUTPUTS) and all(tuple(getattr(al, key).shape) == (0,) for key in api.ALIGN_OUTPUTS)
+    dev = torch.device("cuda", b.gen.device)
+    guard = {key: torch.full((8,), -77, dtype=t, device=dev) for key, t in (("i64", torch.int64), ("i32", torch.int32), ("i16", torch.int16), ("f32", torch.float32))}
+    torch.cuda.synchronize(dev)
+    dtypes = dict(dt_read="i32", dt_start="i64", dt_len="i32", sum="i64", sumsq="i64", vmin="i16", vmax="i16", mean="f32", sd="f32", true_ev="i64", med2="i32", mad4="i32")
+    dout = api.CDetectOut(*(guard[dtypes[key]].data_ptr() for key in api.DETECT_OUTPUTS))
+    aout = api.CAlignOut(guard["i64"].data_ptr(), guard["i64"].data_ptr(), guard["i32"].data_ptr())
+    gen, Lb = b.gen, b.gen.L
+    assert Lb.sqg_batch_detect(gen.ctx, b.handle, C.byref(api.CDetectCfg(3, 6, 1.4, 9.0, 0.2, api.CHUNK_MEDMAD, 1)), C.byref(dout)) == 0
+    off = np.zeros(1, np.int64)
+    ain = api.CAlignIn(guard["i64"].data_ptr(), guard["i32"].data_ptr())
+    assert Lb.sqg_batch_align(gen.ctx, b.handle, C.byref(api.CAlignCfg(*SC.ALIGN_TRUTH)), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ain), C.byref(aout)) == 0
+    torch.cuda.synchronize(dev)
+    assert all(bool((g == -77).all()) for g in guard.values()), "an empty range wrote to an output of detect or align"
+
+
 def _raw_calls(su, b):
     """the C call's name -> the call itself on batch b, nothing wanted: what refuses must refuse before it looks at the outputs"""
     gen, Lb = b.gen, b.gen.L
@@ -193,8 +294,17 @@ def _raw_calls(su, b):
     sc = api.CSiteCfg(256, 128, su.focus, 0, 0, api.CHUNK_F16, api.CHUNK_MEDMAD)
     ec = api.CEventCfg(api.CHUNK_MEDMAD, 1)
     pc = api.CPileupCfg(api.PILEUP_BY_KMER, 0, api.CHUNK_PA, 0, 0, 0, len(su.mean))
+    dc = api.CDetectCfg(3, 6, 1.4, 9.0, 0.2, api.CHUNK_MEDMAD, 1)
+    ac = api.CAlignCfg(*SC.ALIGN_TRUTH)
+    row_off = np.zeros(b.n_reads + 1, np.int64)             # a valid plan without rows, and inputs that are not NULL: both are checked first
+    one = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", gen.device))
+    ain = api.CAlignIn(one.data_ptr(), one.data_ptr())
     n64 = C.c_int64()
     return {
+        "sqg_detect_plan": lambda: Lb.sqg_detect_plan(gen.ctx, b.handle, C.byref(dc), None, C.byref(n64)),
+        "sqg_batch_detect": lambda: Lb.sqg_batch_detect(gen.ctx, b.handle, C.byref(dc), C.byref(api.CDetectOut())),
+        "sqg_batch_align": lambda keep=one: Lb.sqg_batch_align(gen.ctx, b.handle, C.byref(ac), row_off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ain),
+                                                               C.byref(api.CAlignOut())),
         "sqg_chunk_plan": lambda: Lb.sqg_chunk_plan(gen.ctx, b.handle, C.byref(cc), None, C.byref(n64)),
         "sqg_batch_chunks": lambda: Lb.sqg_batch_chunks(gen.ctx, b.handle, C.byref(cc), C.byref(api.CChunkOut())),
         "sqg_batch_chunk_targets": lambda: Lb.sqg_batch_chunk_targets(gen.ctx, b.handle, C.byref(cc), C.byref(api.CChunkTargets())),
@@ -270,7 +380,9 @@ def _lifetime(su, rk, bts, reads):
             assert call() == 0
             continue
         assert call() == -4 and name.encode() in err() and b"handed to a later batch" in err(), f"{name}: {err()}"
-    for call in (lambda: b0.sites(256, 128, su.focus), lambda: b0.events(), lambda: b0.chunks(*SC.CHUNK), lambda: b0.pileup(b0.gen.new_pileup(by="kmer"))):
+    none = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", b0.gen.device))
+    for call in (lambda: b0.sites(256, 128, su.focus), lambda: b0.events(), lambda: b0.chunks(*SC.CHUNK), lambda: b0.pileup(b0.gen.new_pileup(by="kmer")),
+                 lambda: b0.detect(), lambda: b0.align(np.zeros(b0.n_reads + 1, np.int64), none, none.to(torch.int32))):
         with pytest.raises(api.SqgError) as e:
             call()
         assert e.value.code == -4
