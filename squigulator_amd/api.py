@@ -502,26 +502,46 @@ class Batch:
         self.gen, self.handle, self.n_reads = gen, handle, n_reads
         self.res = None
 
+    def _call(self, name, *args):
+        """the library's `name` on this batch; SqgError with the context's text when it fails"""
+        self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, *args), name)
+
+    def _plan(self, name, cfg):
+        """(off [n_reads+1], total) of the plan call `name`: the first row of every read, their number"""
+        off, total = np.zeros(self.n_reads + 1, np.int64), C.c_int64()
+        self._call(name, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total))
+        return off, int(total.value)
+
+    def _table(self, name, args, struct, names, shapes, want, **head):
+        """what sites / events / detect / align share: the Chunks of `head` and, for every output name, a zeroed tensor of its
+        (shape, dtype) in `shapes` if it is wanted, else None; then the library's `name` with `args` and the C struct of their addresses"""
+        import torch
+        dev = torch.device("cuda", self.gen.device)
+        ch = Chunks(**head, **{n: (torch.zeros(shapes[n][0], dtype=shapes[n][1], device=dev) if n in want else None) for n in names})
+        out = _ptrs(struct, (getattr(ch, n) for n in names))
+        torch.cuda.synchronize(dev)                         # (the zero fills and the caller's own work on its inputs, before another stream touches the blocks)
+        self._call(name, *args, C.byref(out))
+        return ch
+
     def run(self):
-        self.gen._chk(self.gen.L.sqg_batch_run(self.gen.ctx, self.handle), "sqg_batch_run")
+        self._call("sqg_batch_run")
         return self
 
     def run_begin(self) -> int:
         """Range sharding: first phase of the run; returns the DEVICE address of this range's per-stream sample counts
         (uint32 [num_workers][4^k], valid until the next run_begin)."""
         p = C.c_void_p()
-        self.gen._chk(self.gen.L.sqg_batch_run_begin(self.gen.ctx, self.handle, C.byref(p)), "sqg_batch_run_begin")
+        self._call("sqg_batch_run_begin", C.byref(p))
         return p.value
 
     def run_end(self, d_before: int | None = None, d_after: int | None = None):
         """second phase; d_before / d_after: device addresses of the counts summed over the earlier / later ranges"""
-        self.gen._chk(self.gen.L.sqg_batch_run_end(self.gen.ctx, self.handle, C.c_void_p(d_before), C.c_void_p(d_after)),
-                      "sqg_batch_run_end")
+        self._call("sqg_batch_run_end", C.c_void_p(d_before), C.c_void_p(d_after))
         return self
 
     def wait(self):
         r = CResult()
-        self.gen._chk(self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)), "sqg_batch_wait")
+        self._call("sqg_batch_wait", C.byref(r))
         self.res = r
         n = r.n_reads
         self.n_samples, self.n_events, self.n_bases = r.n_samples, r.n_events, r.n_bases
@@ -537,19 +557,19 @@ class Batch:
             out = np.empty(self.n_samples, np.int16)
         elif out.dtype != np.int16 or len(out) < self.n_samples:
             raise ValueError("destination too small for the batch's samples")
-        self.gen._chk(self.gen.L.sqg_fetch_signal(self.gen.ctx, self.handle, out.ctypes.data), "sqg_fetch_signal")
+        self._call("sqg_fetch_signal", out.ctypes.data)
         return out[:self.n_samples]
 
     def dwell(self) -> np.ndarray:
         out = np.empty(self.n_events, np.int32)
-        self.gen._chk(self.gen.L.sqg_fetch_dwell(self.gen.ctx, self.handle, out.ctypes.data), "sqg_fetch_dwell")
+        self._call("sqg_fetch_dwell", out.ctypes.data)
         return out
 
     def reads(self):
         """The sampled reads as gen_read returned them (list of bytes); only for batches made by sample()."""
         off = self.sampled["seq_off"]
         buf = np.empty(max(int(off[-1]), 1), np.uint8)
-        self.gen._chk(self.gen.L.sqg_fetch_reads(self.gen.ctx, self.handle, buf.ctypes.data), "sqg_fetch_reads")
+        self._call("sqg_fetch_reads", buf.ctypes.data)
         raw = buf.tobytes()
         return [raw[off[i]:off[i + 1]] for i in range(self.n_reads)]
 
@@ -557,7 +577,7 @@ class Batch:
         """svb-zd encodings of the batch's signals (slow5lib's signal compression), made on the device.
         Returns (bytes as uint8 array, offsets[n_reads+1]); fetch=False leaves the bytes on the device."""
         r = CSvb()
-        self.gen._chk(self.gen.L.sqg_batch_compress(self.gen.ctx, self.handle, C.byref(r)), "sqg_batch_compress")
+        self._call("sqg_batch_compress", C.byref(r))
         off = np.ctypeslib.as_array(r.svb_off, shape=(self.n_reads + 1,)).copy()
         self._svb_bytes = int(r.n_bytes)
         if not fetch:
@@ -573,19 +593,17 @@ class Batch:
         if out is not None and len(out) < n:
             raise ValueError("destination too small for the batch's encodings")
         out = np.empty(n, np.uint8) if out is None else out[:n]
-        self.gen._chk(self.gen.L.sqg_fetch_svb(self.gen.ctx, self.handle, out.ctypes.data), "sqg_fetch_svb")
+        self._call("sqg_fetch_svb", out.ctypes.data)
         return out
 
     def blow5_records(self, profile, flags: int, read_ids, read_number0: int = 0, start_time0: int = 0):
         """the batch's BLOW5 records, framed on the device (sqg_batch_blow5_records) -> (bytes copy, offsets): in stored-block zlib streams,
         or -- BLOW5_HUFFMAN in flags -- in streams of two dynamic-Huffman blocks"""
-        blob = b"".join(read_ids)
-        ioff = np.zeros(len(read_ids) + 1, np.int64)
-        ioff[1:] = np.cumsum([len(r) for r in read_ids])
+        blob, ioff = Blow5Writer._ids(read_ids)
         cp = CProfile(*profile.as_tuple())
         recs, nb, ro = C.c_void_p(), C.c_int64(), C.POINTER(C.c_int64)()
-        self.gen._chk(self.gen.L.sqg_batch_blow5_records(self.gen.ctx, self.handle, C.byref(cp), flags, blob, ioff.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       read_number0, start_time0, C.byref(recs), C.byref(nb), C.byref(ro)), "sqg_batch_blow5_records")
+        self._call("sqg_batch_blow5_records", C.byref(cp), flags, blob, ioff.ctypes.data_as(C.POINTER(C.c_int64)), read_number0, start_time0,
+                   C.byref(recs), C.byref(nb), C.byref(ro))
         data = C.string_at(recs, nb.value) if nb.value else b""
         return data, np.array([ro[i] for i in range(len(read_ids) + 1)], np.int64)
 
@@ -624,23 +642,15 @@ class Batch:
         bounds in stored samples and the range of the RNA adaptor's level shift (sqg_batch_segments, include/sqg_segments.h)"""
         import torch
         self._trimmed("", True)
-        dev = torch.device("cuda", self.gen.device)
-        seg = torch.zeros((self.n_reads, 5), dtype=torch.int64, device=dev)
-        shift = torch.zeros((self.n_reads, 2), dtype=torch.int64, device=dev)
-        out = _ptrs(CSegments, (seg, shift))
-        torch.cuda.synchronize(dev)
-        self.gen._chk(self.gen.L.sqg_batch_segments(self.gen.ctx, self.handle, C.byref(out)), "sqg_batch_segments")
-        return seg, shift
+        shapes = dict(seg=((self.n_reads, 5), torch.int64), shift=((self.n_reads, 2), torch.int64))
+        sg = self._table("sqg_batch_segments", (), CSegments, tuple(shapes), shapes, shapes)
+        return sg.seg, sg.shift
 
     def chunk_plan(self, chunk_len: int, stride: int | None = None, trim: bool = False):
         """(chunk_off [n_reads+1], n_chunks): the first chunk of every read, from the batch's sig_off (sqg_chunk_plan; host only).
         trim=True: of every read's insert (sqg_chunk_plan_trimmed, include/sqg_segments.h; device work)"""
         cfg = self._chunk_cfg(chunk_len, stride, 0, CHUNK_F16, CHUNK_MEDMAD)
-        off = np.zeros(self.n_reads + 1, np.int64)
-        nc = C.c_int64()
-        name = self._trimmed("sqg_chunk_plan", trim)
-        self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nc)), name)
-        return off, int(nc.value)
+        return self._plan(self._trimmed("sqg_chunk_plan", trim), cfg)
 
     def _chunk_job(self, chunk_len, stride, max_label, dtype, norm, trim=False):
         """what chunks() and chunk_targets() share: (cfg, chunk_off, n_chunks, device, new, call) -- new(shape, dtype): an output tensor;
@@ -653,8 +663,7 @@ class Batch:
         def call(name, out, *tensors):
             out = _ptrs(out, tensors)
             torch.cuda.synchronize(dev)                     # (the allocator's pending work on these blocks, if any, before another stream writes them)
-            name = self._trimmed(name, trim)
-            self.gen._chk(getattr(self.gen.L, name)(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), name)
+            self._call(self._trimmed(name, trim), C.byref(cfg), C.byref(out))
         return cfg, off, nc, dev, new, call
 
     def chunks(self, chunk_len: int, stride: int | None = None, max_label: int = 0, dtype="f16", norm="medmad",
@@ -713,13 +722,7 @@ class Batch:
         """(site_off [n_reads+1], n_sites): the first CpG site of every read for windows of win_len samples, `before` of them in front of
         the anchor event (default win_len / 2), the site's base at position `focus` of that event's k-mer (default k / 2)
         (sqg_site_plan, include/sqg_sites.h; device work and a copy-back of the per-read counts)"""
-        return self._site_plan(self._site_cfg(win_len, before, focus, 0, 0, CHUNK_F16, CHUNK_MEDMAD))
-
-    def _site_plan(self, cfg):
-        off = np.zeros(self.n_reads + 1, np.int64)
-        ns = C.c_int64()
-        self.gen._chk(self.gen.L.sqg_site_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ns)), "sqg_site_plan")
-        return off, int(ns.value)
+        return self._plan("sqg_site_plan", self._site_cfg(win_len, before, focus, 0, 0, CHUNK_F16, CHUNK_MEDMAD))
 
     def sites(self, win_len: int, before: int | None = None, focus: int | None = None, ctx_len: int = 0, ctx_before: int | None = None,
               dtype="f16", norm="medmad", outputs=None) -> Chunks:
@@ -731,18 +734,13 @@ class Batch:
         import torch
         cfg = self._site_cfg(win_len, before, focus, ctx_len, ctx_before, dtype, norm)
         want = _want(outputs, SITE_OUTPUTS, "sites")
-        off, ns = self._site_plan(cfg)                      # (validates all of cfg: the shapes below are sane)
-        dev = torch.device("cuda", self.gen.device)
+        off, ns = self._plan("sqg_site_plan", cfg)          # (validates all of cfg: the shapes below are sane)
         L, B = cfg.win_len, cfg.ctx_len
         shapes = dict(signal=((ns, L), torch.float32 if cfg.dtype == CHUNK_F32 else torch.float16), label=((ns,), torch.uint8),
                       site_read=((ns,), torch.int32), site_pos=((ns,), torch.int32), win_start=((ns,), torch.int64),
                       context=((ns, B), torch.uint8), ctx_start=((ns, B + 1), torch.int32),
                       med2=((self.n_reads,), torch.int32), mad4=((self.n_reads,), torch.int32))
-        st = Chunks(n_sites=ns, site_off=off, **{n: (torch.zeros(sh, dtype=dt, device=dev) if n in want else None) for n, (sh, dt) in shapes.items()})
-        out = _ptrs(CSiteOut, (getattr(st, n) for n in SITE_OUTPUTS))
-        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
-        self.gen._chk(self.gen.L.sqg_batch_sites(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_sites")
-        return st
+        return self._table("sqg_batch_sites", (C.byref(cfg),), CSiteOut, SITE_OUTPUTS, shapes, want, n_sites=ns, site_off=off)
 
     def events(self, norm="pa", trim: bool = False, outputs=None) -> Chunks:
         """The per-event signal table of the batch, made on the device (sqg_batch_events, include/sqg_events.h): one row per event in
@@ -761,15 +759,10 @@ class Batch:
             ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
         else:
             ne = int(self.n_events)
-        dev = torch.device("cuda", self.gen.device)
         dts = dict(ev_read=torch.int32, ev_start=torch.int64, ev_len=torch.int32, sum=torch.int64, sumsq=torch.int64, vmin=torch.int16, vmax=torch.int16,
                    kmer=torch.int32, level_raw=torch.int16, seg=torch.uint8, mean=torch.float32, sd=torch.float32, med2=torch.int32, mad4=torch.int32)
-        ev = Chunks(n_events=ne, **{n: (torch.zeros(self.n_reads if n in ("med2", "mad4") else ne, dtype=dts[n], device=dev) if n in want else None)
-                                    for n in EVENT_OUTPUTS})
-        out = _ptrs(CEventOut, (getattr(ev, n) for n in EVENT_OUTPUTS))
-        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
-        self.gen._chk(self.gen.L.sqg_batch_events(self.gen.ctx, self.handle, C.byref(cfg), C.byref(out)), "sqg_batch_events")
-        return ev
+        shapes = {n: (self.n_reads if n in ("med2", "mad4") else ne, dt) for n, dt in dts.items()}
+        return self._table("sqg_batch_events", (C.byref(cfg),), CEventOut, EVENT_OUTPUTS, shapes, want, n_events=ne)
 
     def _detect_cfg(self, cfg, norm, trim):
         _need(self.gen.L, "sqg_batch_detect", "sqg_detect.h", "detect")
@@ -782,13 +775,7 @@ class Batch:
     def detect_plan(self, cfg="dna"):
         """(det_off [n_reads+1], n_rows): the first row of every read in the table Batch.detect() makes with the same cfg
         (sqg_detect_plan, include/sqg_detect.h; device work and a copy-back of the per-read counts)"""
-        return self._detect_plan(self._detect_cfg(cfg, "pa", False))
-
-    def _detect_plan(self, cfg):
-        off = np.zeros(self.n_reads + 1, np.int64)
-        nr = C.c_int64()
-        self.gen._chk(self.gen.L.sqg_detect_plan(self.gen.ctx, self.handle, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nr)), "sqg_detect_plan")
-        return off, int(nr.value)
+        return self._plan("sqg_detect_plan", self._detect_cfg(cfg, "pa", False))
 
     def detect(self, cfg="dna", norm="pa", trim: bool = False, outputs=None) -> Chunks:
         """The table a raw-signal tool's event detector finds in the batch's stored samples, made on the device (sqg_batch_detect,
@@ -801,16 +788,11 @@ class Batch:
         import torch
         c = self._detect_cfg(cfg, norm, trim)
         want = _want(outputs, DETECT_OUTPUTS, "detect")
-        off, nr = self._detect_plan(c)                      # (validates all of cfg, and that the batch has been run)
-        dev = torch.device("cuda", self.gen.device)
+        off, nr = self._plan("sqg_detect_plan", c)          # (validates all of cfg, and that the batch has been run)
         dts = dict(dt_read=torch.int32, dt_start=torch.int64, dt_len=torch.int32, sum=torch.int64, sumsq=torch.int64, vmin=torch.int16, vmax=torch.int16,
                    mean=torch.float32, sd=torch.float32, true_ev=torch.int64, med2=torch.int32, mad4=torch.int32)
-        dt = Chunks(n_rows=nr, det_off=off, **{n: (torch.zeros(self.n_reads if n in ("med2", "mad4") else nr, dtype=dts[n], device=dev) if n in want else None)
-                                                for n in DETECT_OUTPUTS})
-        out = _ptrs(CDetectOut, (getattr(dt, n) for n in DETECT_OUTPUTS))
-        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
-        self.gen._chk(self.gen.L.sqg_batch_detect(self.gen.ctx, self.handle, C.byref(c), C.byref(out)), "sqg_batch_detect")
-        return dt
+        shapes = {n: (self.n_reads if n in ("med2", "mad4") else nr, dt) for n, dt in dts.items()}
+        return self._table("sqg_batch_detect", (C.byref(c),), CDetectOut, DETECT_OUTPUTS, shapes, want, n_rows=nr, det_off=off)
 
     def align(self, row_off, sum, len, cfg=None, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
         """The rows [row_off[r], row_off[r+1]) of sum / len -- Batch.detect()'s det_off, sum and dt_len, or any other segmentation of the
@@ -837,14 +819,9 @@ class Batch:
                 raise SqgError(-1, "align", f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
         keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
         cin = CAlignIn(sum.data_ptr() if sum.numel() else keep.data_ptr(), len.data_ptr() if len.numel() else keep.data_ptr())
-        dts = dict(al_ev=torch.int64, al_cost=torch.int64, al_edge=torch.int32)
-        al = Chunks(n_rows=nr, row_off=off, **{n: (torch.zeros(nr if n == "al_ev" else self.n_reads, dtype=dts[n], device=dev) if n in want else None)
-                                                for n in ALIGN_OUTPUTS})
-        out = _ptrs(CAlignOut, (getattr(al, n) for n in ALIGN_OUTPUTS))
-        torch.cuda.synchronize(dev)                         # (the zero fills and the caller's own work on the rows, before another stream reads them)
-        self.gen._chk(self.gen.L.sqg_batch_align(self.gen.ctx, self.handle, C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin), C.byref(out)),
-                      "sqg_batch_align")
-        return al
+        shapes = dict(al_ev=(nr, torch.int64), al_cost=(self.n_reads, torch.int64), al_edge=(self.n_reads, torch.int32))
+        return self._table("sqg_batch_align", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CAlignOut, ALIGN_OUTPUTS, shapes, want,
+                           n_rows=nr, row_off=off)
 
     def pileup(self, p: Pileup, origin=None):
         """Adds the batch's events to the pileup `p` of SignalGenerator.new_pileup() (sqg_batch_pileup, include/sqg_pileup.h) and returns
@@ -861,8 +838,7 @@ class Batch:
         out = _ptrs(CPileupOut, (getattr(p, n) for n in PILEUP_OUTPUTS))
         st = CPileupStat()
         torch.cuda.synchronize(torch.device("cuda", self.gen.device))     # (the zero fills or the caller's own work on the sums, before another stream adds to them)
-        self.gen._chk(self.gen.L.sqg_batch_pileup(self.gen.ctx, self.handle, C.byref(p.cfg), C.byref(org) if org is not None else None,
-                                                  C.byref(out), C.byref(st)), "sqg_batch_pileup")
+        self._call("sqg_batch_pileup", C.byref(p.cfg), C.byref(org) if org is not None else None, C.byref(out), C.byref(st))
         return int(st.counted), int(st.outside)
 
     def free(self):
@@ -910,20 +886,10 @@ class SignalGenerator:
 
     def stage(self, seqs, workers=None) -> Batch:
         """seqs: list of bytes (reads as gen_read returns them)."""
-        n = len(seqs)
-        off = np.zeros(n + 1, np.int64)
-        if n:
+        off = np.zeros(len(seqs) + 1, np.int64)
+        if len(seqs):
             off[1:] = np.cumsum([len(s) for s in seqs])
-        blob = b"".join(seqs)
-        wk = None
-        if workers is not None:
-            wk = np.ascontiguousarray(workers, np.int32)
-        h = C.c_void_p()
-        rc = self.L.sqg_batch_stage(self.ctx, n, blob, off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                    wk.ctypes.data_as(C.POINTER(C.c_int32)) if wk is not None else None,
-                                    C.byref(h))
-        self._chk(rc, "sqg_batch_stage")
-        return Batch(self, h, n)
+        return self.stage_packed(b"".join(seqs), off, workers)
 
     def stage_packed(self, blob: bytes, off: np.ndarray, workers=None) -> Batch:
         n = len(off) - 1

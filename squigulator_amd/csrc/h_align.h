@@ -26,34 +26,28 @@ extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg
     if (!want_trace && !out->al_cost) return SQG_OK;
     AlignScratch& X = c->align;
     const long long n_rows = (long long)row_off[n];
-    if ((rc = X.d_off.need(c, (size_t)n + 1)) || (rc = X.d_end.need(c, (size_t)n)) || (rc = X.d_level.need(c, (size_t)std::max<long long>(b->n_events, 1)))) return rc;
+    if ((rc = X.d_off.need(c, (size_t)n + 1)) || (rc = X.d_end.need(c, (size_t)n))) return rc;
     if (want_trace && ((rc = X.d_mask.need(c, (size_t)std::max<long long>(n_rows, 1))) || (rc = X.d_lo.need(c, (size_t)std::max<long long>(n_rows, 1))))) return rc;
     const hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(X.d_off.p, row_off, ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     AlignParams P{};
     P.bv = batch_view(c, b);
-    P.row_off = X.d_off.p; P.sum = (const long long*)in->sum; P.len = in->len; P.level_raw = X.d_level.p;
+    P.row_off = X.d_off.p; P.sum = (const long long*)in->sum; P.len = in->len;
     P.stay_pen = cfg->stay_pen; P.skip_pen = cfg->skip_pen; P.cost_cap = cfg->cost_cap;
     P.tr_mask = X.d_mask.p; P.tr_lo = X.d_lo.p; P.end_j = X.d_end.p;
     P.al_ev = (long long*)out->al_ev; P.al_cost = (long long*)out->al_cost; P.al_edge = out->al_edge;
-    // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone)
-    if (b->n_events > 0) {
-        EventParams Q{P.bv, (const float2*)nullptr, b->n_events};
-        Q.level_raw = X.d_level.p;
-        hipLaunchKernelGGL(k_evtab_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
-        HIPCHK(c, hipGetLastError());
-        if ((rc = dbg_sync(c, "k_evtab_scan"))) return rc;
-    }
+    // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone; none for a batch without events, whose reads have no target)
+    EventParams Q{P.bv, (const float2*)nullptr, b->n_events};
+    if (b->n_events > 0 && (rc = evtab_scan_run(c, Q, EVC_LEVEL))) return rc;
+    P.level_raw = Q.level_raw;
     // the forward pass: every read's band row by row, its end, and the trace when a path is wanted
     if (want_trace) hipLaunchKernelGGL(k_align_forward<true>, dim3((unsigned)n), dim3(64), 0, st, P);
     else hipLaunchKernelGGL(k_align_forward<false>, dim3((unsigned)n), dim3(64), 0, st, P);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = dbg_sync(c, "k_align_forward"))) return rc;
+    if ((rc = launched(c, "k_align_forward"))) return rc;
     // the traceback
     if (want_trace) {
         hipLaunchKernelGGL(k_align_trace, dim3((unsigned)n), dim3(64), 0, st, P);
-        HIPCHK(c, hipGetLastError());
-        if ((rc = dbg_sync(c, "k_align_trace"))) return rc;
+        if ((rc = launched(c, "k_align_trace"))) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(st));
     return SQG_OK;

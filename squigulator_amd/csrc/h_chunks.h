@@ -168,8 +168,7 @@ static int stats_run(sqg_ctx* c, sqg_batch* b, ChunkJob& J, int* med2, int* mad4
         hipLaunchKernelGGL(k_chunk_hist_long, dim3(wgs), dim3(CHUNK_WG), 0, st, P, i);
         hipLaunchKernelGGL(k_chunk_select_long, dim3(1), dim3(CHUNK_WG), 0, st, P, i);
     }
-    HIPCHK(c, hipGetLastError());
-    return dbg_sync(c, "k_chunk_stats");
+    return launched(c, "k_chunk_stats");
 }
 
 // The chunk calls' opening: the statistics job and the plan of cfg over its spans

@@ -105,45 +105,55 @@ struct ChunkScratch {
     void release() { *this = ChunkScratch(); }
 };
 
-// device scratch of sqg_site_plan and sqg_batch_sites (h_sites.h): the plan and the per-site records
+// A per-read plan, [n_reads] counts made by a kernel and their running sum: begin() sizes the four arrays (the kernel then writes d_count),
+// finish() copies the counts back, sums them on the host and uploads the sum, give() hands the sum to a plan export's caller.  Every call
+// that plans embeds one of its own: a plan another call could overwrite would be no plan (tests/test_consumer_order.py).  (Bodies below.)
+struct ReadPlan {
+    DevBuf<int> d_count; std::vector<int> h_count;             // [n_reads] rows of every read
+    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first row of every read, device and host
+    int begin(sqg_ctx* c, size_t n);
+    int finish(sqg_ctx* c, size_t n, hipStream_t st);
+    void give(int n, int64_t* off, int64_t* total) const;
+};
+
+// device scratch of sqg_site_plan and sqg_batch_sites (h_sites.h): the plan (k_site_scan<0>'s counts) and the per-site records
 struct SiteScratch {
-    DevBuf<int> d_count; std::vector<int> h_count;             // [n_reads] sites of every read (k_site_scan<0>)
-    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first site of every read, device and host
+    ReadPlan plan;
     DevBuf<SiteRec> d_rec;                                     // [n_sites] (k_site_scan<1> -> k_site_emit)
     DevBuf<uint8_t> d_skip;                                    // [n_reads] the batch's reads shorter than a k-mer
     const void* plan_of = nullptr; unsigned long long plan_run = 0; int plan_key[3] = {0, 0, 0};   // the batch (and its run index) and the win_len / before / focus the plan was last made for
     void release() { *this = SiteScratch(); }
 };
 
-// device scratch of sqg_batch_events (h_events_table.h): what the reduce pass needs of columns the caller did not ask for
+// device scratch of k_evtab_scan's columns (h_events_table.h: evtab_scan_run), [n_events] each: those a call's later passes need and its
+// caller did not ask for.  sqg_batch_events, sqg_batch_pileup, sqg_batch_detect and sqg_batch_align.
 struct EventScratch {
-    DevBuf<long long> d_start;                                 // [n_events] first stored sample of every event within its read (k_evtab_scan)
-    DevBuf<int> d_read;                                        // [n_events] event -> read
+    DevBuf<long long> d_start;                                 // first stored sample of every event within its read
+    DevBuf<int> d_read;                                        // event -> read
+    DevBuf<uint32_t> d_kmer;                                   // pore-table row of every event
+    DevBuf<uint8_t> d_seg;                                     // its segment
+    DevBuf<int16_t> d_level;                                   // its level_raw
     void release() { *this = EventScratch(); }
 };
 
-// device scratch of sqg_batch_pileup (h_pileup.h): the scan pass's columns the key or a split needs, the reads' origins, the counters
+// device scratch of sqg_batch_pileup (h_pileup.h): the reads' origins, the counters
 struct PileupScratch {
-    DevBuf<uint32_t> d_kmer;                                   // [n_events] pore-table row of every event (k_evtab_scan)
-    DevBuf<uint8_t> d_seg;                                     // [n_events] its segment
     DevBuf<PileRead> d_pr; std::vector<PileRead> h_pr;         // [n_reads] origin and insert of every read, device and host
     DevBuf<unsigned long long> d_stat;                         // {counted, outside}
     void release() { *this = PileupScratch(); }
 };
 
-// device scratch of sqg_detect_plan and sqg_batch_detect (h_detect.h): the plan, and the columns the row pass needs when the caller did not ask for them
+// device scratch of sqg_detect_plan and sqg_batch_detect (h_detect.h): the plan (k_detect_walk<false>'s counts), and the columns the row pass needs when the caller did not ask for them
 struct DetectScratch {
-    DevBuf<int> d_count; std::vector<int> h_count;             // [n_reads] rows of every read (k_detect_walk<false>)
-    DevBuf<long long> d_off; std::vector<long long> h_off;     // [n_reads+1] first row of every read, device and host
+    ReadPlan plan;
     DevBuf<long long> d_start;                                 // [n_rows] first stored sample of every row within its read (k_detect_walk<true>)
     DevBuf<int> d_read;                                        // [n_rows] row -> read
     void release() { *this = DetectScratch(); }
 };
 
-// device scratch of sqg_batch_align (h_align.h): the row offsets, the targets' levels, the trace of the forward pass and every read's end
+// device scratch of sqg_batch_align (h_align.h): the row offsets, the trace of the forward pass and every read's end
 struct AlignScratch {
     DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
-    DevBuf<int16_t> d_level;                                   // [n_events] level_raw of every event (k_evtab_scan)
     DevBuf<ulonglong2> d_mask; DevBuf<int> d_lo;               // [n_rows] the two move-code bits of every band cell, the band's first target
     DevBuf<int> d_end;                                         // [n_reads] the target the best path ends at, -1: none
     void release() { *this = AlignScratch(); }
@@ -285,7 +295,7 @@ struct sqg_ctx {
     void* b5_reader = nullptr; int b5_reader_buf = -1; void (*b5_reader_drain)(void* writer, bool unbind) = nullptr;
     ChunkScratch chunk;                                        // sqg_batch_chunks, sqg_batch_chunk_targets (h_chunks.h, h_targets.h)
     SiteScratch site;                                          // sqg_site_plan, sqg_batch_sites (h_sites.h)
-    EventScratch event;                                        // sqg_batch_events (h_events_table.h)
+    EventScratch event;                                        // k_evtab_scan's columns (h_events_table.h: evtab_scan_run)
     PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
     DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
     AlignScratch align;                                        // sqg_batch_align (h_align.h)
@@ -511,6 +521,35 @@ static int dbg_sync(sqg_ctx* c, const char* what) {
     if (e != hipSuccess) { c->err = std::string(what) + ": " + hipGetErrorString(e); fprintf(stderr, "[sqg] %s\n", c->err.c_str()); return SQG_EDEVICE; }
     fprintf(stderr, "[sqg] %s ok\n", what);
     return SQG_OK;
+}
+// ... behind every launch of a consumer call: the launch's own error, then the aid
+static int launched(sqg_ctx* c, const char* kernel) {
+    HIPCHK(c, hipGetLastError());
+    return dbg_sync(c, kernel);
+}
+
+inline int ReadPlan::begin(sqg_ctx* c, size_t n) {
+    int rc;
+    if ((rc = d_count.need(c, n)) || (rc = d_off.need(c, n + 1))) return rc;
+    h_count.resize(n); h_off.resize(n + 1);
+    return SQG_OK;
+}
+// behind the counting kernel's launch on st: its error, the one synchronisation a plan needs, and a second one behind the upload: h_off is
+// the scratch's, the copy has left it before anybody rewrites it
+inline int ReadPlan::finish(sqg_ctx* c, size_t n, hipStream_t st) {
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_count.data(), d_count.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    h_off[0] = 0;
+    for (size_t i = 0; i < n; i++) h_off[i + 1] = h_off[i] + h_count[i];
+    HIPCHK(c, hipMemcpyAsync(d_off.p, h_off.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return SQG_OK;
+}
+// (an empty batch has no plan, and none is read: one offset, 0 rows)
+inline void ReadPlan::give(int n, int64_t* off, int64_t* total) const {
+    if (off) { off[0] = 0; for (int i = 1; i <= n; i++) off[i] = (int64_t)h_off[(size_t)i]; }
+    *total = n ? (int64_t)h_off[(size_t)n] : 0;
 }
 
 // phase 0: the whole run; 1: up to the per-stream sample counts of a split batch (sqg_batch_run_begin); 2: the rest

@@ -23,27 +23,17 @@ static DetectParams detect_params(const sqg_ctx* c, const sqg_batch* b, const sq
     return P;
 }
 
-// The plan of a non-empty batch that has finished and owns its results: DetectScratch::h_off [n+1] and its copy on the device.
-// k_detect_walk<false>, a copy-back of n counts and the one synchronisation the plan needs.  It is made afresh by every call: it
-// depends on the samples themselves, not only on the batch's geometry, and one walk costs less than a plan that no longer fits them.
+// The plan of a non-empty batch that has finished and owns its results: DetectScratch::plan (h_common.h: ReadPlan), h_off [n+1] and its
+// copy on the device, from k_detect_walk<false>'s counts.  It is made afresh by every call: it depends on the samples themselves, not
+// only on the batch's geometry, and one walk costs less than a plan that no longer fits them.
 static int detect_plan_run(sqg_ctx* c, sqg_batch* b, const sqg_detect_cfg_t* cfg) {
-    DetectScratch& X = c->detect;
+    ReadPlan& X = c->detect.plan;
     const size_t n = (size_t)b->n;
-    int rc;
-    if ((rc = X.d_count.need(c, n)) || (rc = X.d_off.need(c, n + 1))) return rc;
-    const hipStream_t st = c->stream;
-    X.h_count.resize(n); X.h_off.resize(n + 1);
+    if (int rc = X.begin(c, n)) return rc;
     DetectParams P = detect_params(c, b, cfg);
     P.count = X.d_count.p;
-    hipLaunchKernelGGL(k_detect_walk<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, P);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(X.h_count.data(), X.d_count.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    X.h_off[0] = 0;
-    for (size_t i = 0; i < n; i++) X.h_off[i + 1] = X.h_off[i] + X.h_count[i];
-    HIPCHK(c, hipMemcpyAsync(X.d_off.p, X.h_off.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));                                // (h_off is the scratch's: the copy has left it before anybody rewrites it)
-    return SQG_OK;
+    hipLaunchKernelGGL(k_detect_walk<false>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, P);
+    return X.finish(c, n, c->stream);
 }
 
 extern "C" int sqg_detect_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_detect_cfg_t* cfg, int64_t* det_off, int64_t* n_rows) {
@@ -53,10 +43,8 @@ extern "C" int sqg_detect_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_detect_cf
     const Check K{c, who};
     if ((rc = K.null(n_rows, "n_rows")) || (rc = K.ran(b))) return rc;
     if ((rc = chunk_owned(c, b, who, c->use_dwell_stream))) return rc;
-    if (b->n == 0) { if (det_off) det_off[0] = 0; *n_rows = 0; return SQG_OK; }
-    if ((rc = detect_plan_run(c, b, cfg))) return rc;
-    if (det_off) for (int i = 0; i <= b->n; i++) det_off[i] = (int64_t)c->detect.h_off[(size_t)i];
-    *n_rows = (int64_t)c->detect.h_off[(size_t)b->n];
+    if (b->n > 0 && (rc = detect_plan_run(c, b, cfg))) return rc;
+    c->detect.plan.give(b->n, det_off, n_rows);
     return SQG_OK;
 }
 
@@ -66,50 +54,42 @@ extern "C" int sqg_batch_detect(sqg_ctx_t* c, sqg_batch_t* b, const sqg_detect_c
     if (rc) return rc;
     const Check K{c, who};
     if ((rc = K.null(out, "out")) || (rc = K.ran(b))) return rc;
-    const bool want_norm = out->mean || out->sd;
-    const bool want_stats = out->med2 || out->mad4 || (want_norm && cfg->norm == SQG_CHUNK_MEDMAD);
-    const bool want_rows = want_norm || out->sum || out->sumsq || out->vmin || out->vmax || out->dt_len || out->true_ev;
+    EventParams Q{};
+    const EventWants want = evtab_outputs(Q, out, cfg->norm);
+    const bool want_rows = want.sums || out->dt_len || out->true_ev;
     const bool want_walk = want_rows || out->dt_read || out->dt_start;
     // the statistics job as sqg_batch_events opens it: the inserts' spans only where the statistics are wanted over them
     ChunkJob J;
-    if ((rc = spans_open(c, b, who, c->use_dwell_stream, want_stats && cfg->trim == 1, &J)) || J.P.bv.n_reads == 0) return rc;
+    if ((rc = spans_open(c, b, who, c->use_dwell_stream, want.stats && cfg->trim == 1, &J)) || J.P.bv.n_reads == 0) return rc;
     const int n = b->n;
     const hipStream_t st = J.st;
-    if (want_stats && (rc = stats_run(c, b, J, out->med2, out->mad4))) return rc;
+    if (want.stats && (rc = stats_run(c, b, J, out->med2, out->mad4))) return rc;
     if (want_walk) {
         DetectScratch& X = c->detect;
         // pass 1, the plan: every read's rows
         if ((rc = detect_plan_run(c, b, cfg))) return rc;
-        const long long n_rows = X.h_off[(size_t)n];
+        const long long n_rows = X.plan.h_off[(size_t)n];
         if (n_rows > 0) {
             if (!out->dt_start && (rc = X.d_start.need(c, (size_t)n_rows))) return rc;
             if (!out->dt_read && (rc = X.d_read.need(c, (size_t)n_rows))) return rc;
             // pass 2, the same walk again: where every row starts, and its read
             DetectParams P = detect_params(c, b, cfg);
-            P.det_off = X.d_off.p;
+            P.det_off = X.plan.d_off.p;
             P.dt_start = out->dt_start ? (long long*)out->dt_start : X.d_start.p;
             P.dt_read = out->dt_read ? out->dt_read : X.d_read.p;
             hipLaunchKernelGGL(k_detect_walk<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, P);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = dbg_sync(c, "k_detect_walk"))) return rc;
+            if ((rc = launched(c, "k_detect_walk"))) return rc;
             if (want_rows) {
-                EventParams Q{J.P.bv, want_stats ? J.P.consts : (const float2*)nullptr, b->n_events};
-                DetectRowParams U{X.d_off.p, n_rows, P.dt_start, P.dt_read, out->dt_len, (long long*)out->true_ev, nullptr};
+                Q.bv = J.P.bv; Q.consts = want.stats ? J.P.consts : (const float2*)nullptr; Q.n_events = b->n_events;
+                DetectRowParams U{X.plan.d_off.p, n_rows, P.dt_start, P.dt_read, out->dt_len, (long long*)out->true_ev, nullptr};
                 // true_ev: where every true event starts (k_events_table.h's scan pass, that column alone)
                 if (out->true_ev && b->n_events > 0) {
-                    if ((rc = c->event.d_start.need(c, (size_t)b->n_events))) return rc;
-                    Q.ev_start = c->event.d_start.p;
-                    hipLaunchKernelGGL(k_evtab_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
-                    HIPCHK(c, hipGetLastError());
-                    if ((rc = dbg_sync(c, "k_evtab_scan"))) return rc;
+                    if ((rc = evtab_scan_run(c, Q, EVC_START))) return rc;
                     U.ev_start = Q.ev_start;
                 } else U.true_ev = nullptr;
                 // pass 3, the rows: their lengths, the sums of their samples, mean / sd from them, the event under their first sample
-                Q.sum = (long long*)out->sum; Q.sumsq = (long long*)out->sumsq; Q.vmin = out->vmin; Q.vmax = out->vmax; Q.mean = out->mean; Q.sd = out->sd;
-                const unsigned wgs = (unsigned)std::min<long long>((n_rows + CHUNK_WG - 1) / CHUNK_WG, 32LL * c->num_cu);
-                dispatch(false, cfg->norm == SQG_CHUNK_PA, [&](auto, auto A) { hipLaunchKernelGGL(k_detect_rows<decltype(A)::value>, dim3(wgs), dim3(CHUNK_WG), 0, st, Q, U); });
-                HIPCHK(c, hipGetLastError());
-                if ((rc = dbg_sync(c, "k_detect_rows"))) return rc;
+                dispatch(false, cfg->norm == SQG_CHUNK_PA, [&](auto, auto A) { hipLaunchKernelGGL(k_detect_rows<decltype(A)::value>, dim3(flat_grid(c, n_rows)), dim3(CHUNK_WG), 0, st, Q, U); });
+                if ((rc = launched(c, "k_detect_rows"))) return rc;
             }
         }
     }

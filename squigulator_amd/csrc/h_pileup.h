@@ -34,13 +34,7 @@ extern "C" int sqg_batch_pileup(sqg_ctx_t* c, sqg_batch_t* b, const sqg_pileup_c
     if ((rc = spans_open(c, b, who, c->use_dwell_stream, want_stats && cfg->trim == 1, &J)) || J.P.bv.n_reads == 0 || b->n_events == 0) return rc;
     const hipStream_t st = J.st;
     if (want_stats && (rc = stats_run(c, b, J, nullptr, nullptr))) return rc;
-    EventScratch& X = c->event;
     PileupScratch& Y = c->pileup;
-    const size_t ne = (size_t)b->n_events;
-    const bool want_kmer = by_kmer || split_meth;
-    if ((rc = X.d_start.need(c, ne)) || (rc = X.d_read.need(c, ne))) return rc;
-    if (want_kmer && (rc = Y.d_kmer.need(c, ne))) return rc;
-    if (by_kmer && (rc = Y.d_seg.need(c, ne))) return rc;
     if ((rc = Y.d_pr.need(c, (size_t)n)) || (rc = Y.d_stat.need(c, 2))) return rc;
     // every read's origin and insert: L from its events (ne0 = attached length - k + 1), 0 for a stand-in read
     EventParams Q{J.P.bv, want_stats ? J.P.consts : (const float2*)nullptr, b->n_events};
@@ -61,12 +55,8 @@ extern "C" int sqg_batch_pileup(sqg_ctx_t* c, sqg_batch_t* b, const sqg_pileup_c
     }
     HIPCHK(c, hipMemcpyAsync(Y.d_pr.p, Y.h_pr.data(), (size_t)n * sizeof(PileRead), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemsetAsync(Y.d_stat.p, 0, 2 * sizeof(unsigned long long), st));
-    Q.ev_start = X.d_start.p; Q.ev_read = X.d_read.p;
-    Q.kmer = want_kmer ? Y.d_kmer.p : (uint32_t*)nullptr; Q.seg = by_kmer ? Y.d_seg.p : (uint8_t*)nullptr;
     // pass 1, scan (k_events_table.h): where every event starts, its read, and k-mer / segment where the key or a split needs them
-    hipLaunchKernelGGL(k_evtab_scan, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = dbg_sync(c, "k_evtab_scan"))) return rc;
+    if ((rc = evtab_scan_run(c, Q, EVC_START | EVC_READ | (by_kmer || split_meth ? EVC_KMER : 0) | (by_kmer ? EVC_SEG : 0)))) return rc;
     // pass 2: the samples of the events that count, their mean / sd, the adds
     PileupParams U{};
     U.pr = Y.d_pr.p; U.kmer = Q.kmer; U.seg = Q.seg;
@@ -75,10 +65,8 @@ extern "C" int sqg_batch_pileup(sqg_ctx_t* c, sqg_batch_t* b, const sqg_pileup_c
     U.n = out->n; U.dwell = (long long*)out->dwell; U.dwell_sq = (long long*)out->dwell_sq;
     U.mean_sum = (long long*)out->mean_sum; U.mean_sq = (long long*)out->mean_sq; U.sd_sum = (long long*)out->sd_sum;
     U.stat = Y.d_stat.p;
-    const unsigned wgs = (unsigned)std::min<long long>((b->n_events + CHUNK_WG - 1) / CHUNK_WG, 32LL * c->num_cu);
-    dispatch(false, cfg->norm == SQG_CHUNK_PA, [&](auto, auto A) { hipLaunchKernelGGL(k_pileup<decltype(A)::value>, dim3(wgs), dim3(CHUNK_WG), 0, st, Q, U); });
-    HIPCHK(c, hipGetLastError());
-    if ((rc = dbg_sync(c, "k_pileup"))) return rc;
+    dispatch(false, cfg->norm == SQG_CHUNK_PA, [&](auto, auto A) { hipLaunchKernelGGL(k_pileup<decltype(A)::value>, dim3(flat_grid(c, b->n_events)), dim3(CHUNK_WG), 0, st, Q, U); });
+    if ((rc = launched(c, "k_pileup"))) return rc;
     unsigned long long h_stat[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(h_stat, Y.d_stat.p, sizeof h_stat, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));

@@ -23,36 +23,29 @@ static SiteParams site_params(sqg_ctx* c, sqg_batch* b, const sqg_site_cfg_t* cf
     Q.bv = batch_view(c, b);
     Q.skip = b->short_read.empty() ? nullptr : c->site.d_skip.p;
     Q.L = cfg->win_len; Q.before = cfg->before; Q.focus = cfg->focus; Q.B = cfg->ctx_len; Q.cb = cfg->ctx_before;
-    Q.count = c->site.d_count.p; Q.site_off = c->site.d_off.p; Q.rec = c->site.d_rec.p;
+    Q.count = c->site.plan.d_count.p; Q.site_off = c->site.plan.d_off.p; Q.rec = c->site.d_rec.p;
     return Q;
 }
 
-// The plan of a non-empty batch that has finished and owns its results and dwells: SiteScratch::h_off [n+1] and its copy on the device.
-// k_site_scan<0>, a copy-back of n counts and the one synchronisation the plan needs -- once per batch and (win_len, before, focus): a
-// call that follows another with the same three (the plan, then the sites) finds it in the scratch.
+// The plan of a non-empty batch that has finished and owns its results and dwells: SiteScratch::plan (h_common.h: ReadPlan), h_off [n+1]
+// and its copy on the device, from k_site_scan<0>'s counts -- once per batch and (win_len, before, focus): a call that follows another
+// with the same three (the plan, then the sites) finds it in the scratch, whatever other calls ran between the two.
 static int site_plan_run(sqg_ctx* c, sqg_batch* b, const sqg_site_cfg_t* cfg) {
     SiteScratch& X = c->site;
     const size_t n = (size_t)b->n;
-    if (X.plan_of == (const void*)b && X.plan_run == b->run_idx && X.h_off.size() == n + 1 &&
+    if (X.plan_of == (const void*)b && X.plan_run == b->run_idx && X.plan.h_off.size() == n + 1 &&
         X.plan_key[0] == cfg->win_len && X.plan_key[1] == cfg->before && X.plan_key[2] == cfg->focus) return SQG_OK;
     X.plan_of = nullptr;                                                // (until the new plan is there)
     int rc;
-    if ((rc = X.d_count.need(c, n)) || (rc = X.d_off.need(c, n + 1))) return rc;
+    if ((rc = X.plan.begin(c, n))) return rc;
     const hipStream_t st = c->stream;
     if (!b->short_read.empty()) {
         if ((rc = X.d_skip.need(c, n))) return rc;
         HIPCHK(c, hipMemcpyAsync(X.d_skip.p, b->short_read.data(), n, hipMemcpyHostToDevice, st));
     }
-    X.h_count.resize(n); X.h_off.resize(n + 1);
     const SiteParams Q = site_params(c, b, cfg);
     hipLaunchKernelGGL(k_site_scan<0>, dim3((unsigned)n), dim3(CHUNK_WG), 0, st, Q);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(X.h_count.data(), X.d_count.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    X.h_off[0] = 0;
-    for (size_t i = 0; i < n; i++) X.h_off[i + 1] = X.h_off[i] + X.h_count[i];
-    HIPCHK(c, hipMemcpyAsync(X.d_off.p, X.h_off.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));                                // (h_off is the scratch's: the copy has left it before anybody rewrites it)
+    if ((rc = X.plan.finish(c, n, st))) return rc;
     X.plan_of = b; X.plan_run = b->run_idx;
     X.plan_key[0] = cfg->win_len; X.plan_key[1] = cfg->before; X.plan_key[2] = cfg->focus;
     return SQG_OK;
@@ -64,10 +57,8 @@ extern "C" int sqg_site_plan(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_t*
     if (rc) return rc;
     if ((rc = Check{c, who}.null(n_sites, "n_sites"))) return rc;
     if ((rc = chunk_owned(c, b, who, c->use_dwell_stream))) return rc;
-    if (b->n == 0) { if (site_off) site_off[0] = 0; *n_sites = 0; return SQG_OK; }
-    if ((rc = site_plan_run(c, b, cfg))) return rc;
-    if (site_off) for (int i = 0; i <= b->n; i++) site_off[i] = (int64_t)c->site.h_off[(size_t)i];
-    *n_sites = (int64_t)c->site.h_off[(size_t)b->n];
+    if (b->n > 0 && (rc = site_plan_run(c, b, cfg))) return rc;
+    c->site.plan.give(b->n, site_off, n_sites);
     return SQG_OK;
 }
 
@@ -82,7 +73,7 @@ extern "C" int sqg_batch_sites(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_
     if ((rc = spans_open(c, b, who, c->use_dwell_stream, false, &J)) || J.P.bv.n_reads == 0) return rc;
     if ((rc = site_plan_run(c, b, cfg))) return rc;
     const int n = b->n;
-    const long long n_sites = c->site.h_off[(size_t)n];
+    const long long n_sites = c->site.plan.h_off[(size_t)n];
     const hipStream_t st = J.st;
     const bool want_rows = n_sites > 0 && (out->signal || out->context || out->ctx_start);
     const bool want_stats = out->med2 || out->mad4 || (out->signal && n_sites > 0 && cfg->norm == SQG_CHUNK_MEDMAD);
@@ -102,8 +93,7 @@ extern "C" int sqg_batch_sites(sqg_ctx_t* c, sqg_batch_t* b, const sqg_site_cfg_
                 hipLaunchKernelGGL((k_site_emit<decltype(F)::value, decltype(A)::value>), dim3(wgs), dim3(CHUNK_WG), 0, st, Q);
             });
         }
-        HIPCHK(c, hipGetLastError());
-        if ((rc = dbg_sync(c, "k_site_emit"))) return rc;
+        if ((rc = launched(c, "k_site_emit"))) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(st));
     return SQG_OK;

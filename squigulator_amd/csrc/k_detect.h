@@ -179,26 +179,14 @@ __device__ __forceinline__ long long detect_true_ev(const long long* ev_start, c
 
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_detect_rows(EventParams Q, DetectRowParams U) {
-    const int lane = threadIdx.x & 63;
     const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.bv.sig);
-    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < U.n_rows; base += (long long)gridDim.x * CHUNK_WG) {
-        const long long i = base + threadIdx.x;
-        const bool have = i < U.n_rows;
+    evtab_for_rows(U.n_rows, [&](const long long i, const bool have, const int lane) {
         const auto [r, len, s0] = have ? detect_row(U, Q.bv, i) : EventAt{0, 0, 0};
         const bool reduce = Q.sum || Q.sumsq || Q.vmin || Q.vmax || Q.mean || Q.sd;      // (the same in every lane)
         const EventAcc A = reduce ? evtab_take(W, have, len, s0, lane) : EventAcc{0, 0, 0, 0};
-        if (!have) continue;
+        if (!have) return;
         if (U.dt_len) U.dt_len[i] = len;
         if (U.true_ev) U.true_ev[i] = detect_true_ev(U.ev_start, Q.bv.reads[r], Q.bv.rna, s0 - Q.bv.sig_off[r]);
-        if (Q.sum) Q.sum[i] = A.sum;
-        if (Q.sumsq) Q.sumsq[i] = (long long)A.sq;
-        if (Q.vmin) Q.vmin[i] = (int16_t)A.mn;
-        if (Q.vmax) Q.vmax[i] = (int16_t)A.mx;
-        if (Q.mean || Q.sd) {
-            float mean, sd;
-            evtab_derive<PA>(Q, r, len, A, &mean, &sd);
-            if (Q.mean) Q.mean[i] = mean;
-            if (Q.sd) Q.sd[i] = sd;
-        }
-    }
+        evtab_store<PA>(Q, i, r, len, A);
+    });
 }

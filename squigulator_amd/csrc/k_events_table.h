@@ -132,25 +132,41 @@ __device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, 
     }
 }
 
+// The six columns of sums of row i (an event of the table, a row of the detector's) of read r, mean / sd among them: those the caller
+// asked for.  k_evtab_reduce and k_detect_rows (k_detect.h).
+template <bool PA>
+__device__ __forceinline__ void evtab_store(const EventParams& Q, const long long i, const int r, const int len, const EventAcc& A) {
+    if (Q.sum) Q.sum[i] = A.sum;
+    if (Q.sumsq) Q.sumsq[i] = (long long)A.sq;
+    if (Q.vmin) Q.vmin[i] = (int16_t)A.mn;
+    if (Q.vmax) Q.vmax[i] = (int16_t)A.mx;
+    if (Q.mean || Q.sd) {
+        float mean, sd;
+        evtab_derive<PA>(Q, r, len, A, &mean, &sd);
+        if (Q.mean) Q.mean[i] = mean;
+        if (Q.sd) Q.sd[i] = sd;
+    }
+}
+
+// A flat grid over n rows, one row per lane, in as many trips as the grid needs: f(i, have, lane) for row i of every trip, `have`
+// saying whether there is such a row.  f is called in ALL 64 lanes of a wavefront on every trip the wavefront makes, the lanes behind
+// the last row included: evtab_take and k_pileup's ballots are wave-wide, so f reaches them before it returns for want of a row.
+// k_evtab_reduce, k_pileup (k_pileup.h) and k_detect_rows (k_detect.h).
+template <class F>
+__device__ __forceinline__ void evtab_for_rows(const long long n, F f) {
+    const int lane = threadIdx.x & 63;
+    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < n; base += (long long)gridDim.x * CHUNK_WG) {
+        const long long i = base + threadIdx.x;
+        f(i, i < n, lane);
+    }
+}
+
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_evtab_reduce(EventParams Q) {
-    const int lane = threadIdx.x & 63;
     const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.bv.sig);              // the slab in aligned words: sample s is half s & 1 of word s >> 1
-    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
-        const long long i = base + threadIdx.x;
-        const bool have = i < Q.n_events;
+    evtab_for_rows(Q.n_events, [&](const long long i, const bool have, const int lane) {
         const auto [r, len, s0] = have ? evtab_event(Q, i) : EventAt{0, 0, 0};
         const EventAcc A = evtab_take(W, have, len, s0, lane);
-        if (!have) continue;
-        if (Q.sum) Q.sum[i] = A.sum;
-        if (Q.sumsq) Q.sumsq[i] = (long long)A.sq;
-        if (Q.vmin) Q.vmin[i] = (int16_t)A.mn;
-        if (Q.vmax) Q.vmax[i] = (int16_t)A.mx;
-        if (Q.mean || Q.sd) {
-            float mean, sd;
-            evtab_derive<PA>(Q, r, len, A, &mean, &sd);
-            if (Q.mean) Q.mean[i] = mean;
-            if (Q.sd) Q.sd[i] = sd;
-        }
-    }
+        if (have) evtab_store<PA>(Q, i, r, len, A);
+    });
 }

@@ -26,13 +26,10 @@ __device__ __forceinline__ long long pileup_q(const float x) { return (long long
 
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams U) {
-    const int lane = threadIdx.x & 63;
     const uint32_t* W = reinterpret_cast<const uint32_t*>(Q.bv.sig);
     const long long width = U.hi - U.lo;
     const bool want_samples = U.mean_sum || U.mean_sq || U.sd_sum;
-    for (long long base = (long long)blockIdx.x * CHUNK_WG; base < Q.n_events; base += (long long)gridDim.x * CHUNK_WG) {
-        const long long i = base + threadIdx.x;
-        const bool have = i < Q.n_events;
+    evtab_for_rows(Q.n_events, [&](const long long i, const bool have, const int lane) {
         const auto [r, len, s0] = have ? evtab_event(Q, i) : EventAt{0, 0, 0};
         long long key = 0;
         bool eligible = false;
@@ -65,10 +62,10 @@ __global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams
             if (m_in) __hip_atomic_fetch_add(U.stat, (unsigned long long)__popcll(m_in), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (m_out) __hip_atomic_fetch_add(U.stat + 1, (unsigned long long)__popcll(m_out), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (!inside) continue;
+        if (!inside) return;
         const long long at = (long long)plane * width + (key - U.lo);
         if (U.n) __hip_atomic_fetch_add(U.n + at, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (len <= 0) continue;                                                   // no sample, no mean: n only
+        if (len <= 0) return;                                                     // no sample, no mean: n only
         if (U.dwell) __hip_atomic_fetch_add(U.dwell + at, (long long)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (U.dwell_sq) __hip_atomic_fetch_add(U.dwell_sq + at, (long long)len * len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (want_samples) {
@@ -79,5 +76,5 @@ __global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams
             if (U.mean_sq) __hip_atomic_fetch_add(U.mean_sq + at, (long long)((unsigned long long)qm * (unsigned long long)qm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (U.sd_sum) __hip_atomic_fetch_add(U.sd_sum + at, pileup_q(sd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
+    });
 }

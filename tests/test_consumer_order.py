@@ -3,6 +3,8 @@ and site plans, the event columns, the detector's plan, the aligner's levels): w
 ran before it on that context.  Every call alone on a fresh context is the reference; the same calls in the listed order, in reverse,
 and across two consecutive batches -- those for batch 0 made after batch 1 has run, while batch 0 still owns its device results --
 must give the same tensors, bit for bit."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
@@ -100,6 +102,48 @@ def _same(got, want, what):
         else:
             assert g == w, f"{what}: {key}"
     return n
+
+
+def _sites_raw(b, off, ns):
+    """sqg_batch_sites as Batch.sites(64, ctx_len=5) calls it, through the library itself and with no plan call in front of it: the
+    tensors of a table of ns sites"""
+    cfg = api.CSiteCfg(64, 32, b.gen.kmer_size // 2, 5, 2, api.CHUNK_F16, api.CHUNK_MEDMAD)
+    dev = torch.device("cuda", b.gen.device)
+    shapes = dict(signal=((ns, 64), torch.float16), label=((ns,), torch.uint8), site_read=((ns,), torch.int32), site_pos=((ns,), torch.int32),
+                  win_start=((ns,), torch.int64), context=((ns, 5), torch.uint8), ctx_start=((ns, 6), torch.int32),
+                  med2=((b.n_reads,), torch.int32), mad4=((b.n_reads,), torch.int32))
+    st = api.Chunks(n_sites=ns, site_off=off, **{n: torch.zeros(shapes[n][0], dtype=shapes[n][1], device=dev) for n in api.SITE_OUTPUTS})
+    out = api._ptrs(api.CSiteOut, (getattr(st, n) for n in api.SITE_OUTPUTS))
+    torch.cuda.synchronize(dev)
+    rc = b.gen.L.sqg_batch_sites(b.gen.ctx, b.handle, ctypes.byref(cfg), ctypes.byref(out))
+    assert rc == 0, b.gen.L.sqg_last_error(b.gen.ctx).decode()
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [api.MODE_CERTIFIED, api.MODE_EXACT], ids=["certified", "exact"])
+def test_site_plan_found_in_the_scratch_behind_other_plans(mode):
+    """sqg_batch_sites finds the plan sqg_site_plan left in the scratch when (win_len, before, focus) agree.  Batch.sites() always plans
+    right in front of it; here the detector's plan -- the other per-read plan of the context -- and an event table run between the two,
+    and the sites must still be those of Batch.sites() alone on a fresh context, bit for bit.  Both orders of the two plans."""
+    gen, bs = _batches("r9_meth", mode, 1)
+    want = bs[0].sites(64, ctx_len=5)
+    _close(gen, bs)
+    assert want.n_sites > 0
+    for what in ("site plan first", "detect plan first"):
+        gen, bs = _batches("r9_meth", mode, 1)
+        b = bs[0]
+        if what == "detect plan first":
+            b.detect_plan("dna")
+        off, ns = b.site_plan(64)
+        b.detect("dna")
+        b.events("medmad")
+        # (the plan call again finds the plan in the scratch, as the raw call will, and runs no kernel: a plan that changed is reported
+        # here, before a kernel writes that plan's rows into tensors sized by the first one)
+        off2, ns2 = b.site_plan(64)
+        assert ns2 == ns == want.n_sites and np.array_equal(off2, off), f"r9_meth {what}: the plan in the scratch"
+        assert _same(_sites_raw(b, off, ns), want, f"r9_meth {what}") > 0
+        _close(gen, bs)
 
 
 @pytest.mark.gpu

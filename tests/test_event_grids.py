@@ -321,10 +321,10 @@ def _assert_rows_behind_cap(got, want, keys, cap, n, what):
 @pytest.mark.gpu
 @pytest.mark.parametrize("norm", ["pa", "medmad"])
 def test_events_behind_the_first_trip_of_the_grid(norm):
-    """k_events_table.h:139, `base += gridDim.x * CHUNK_WG` of k_evtab_reduce: its second trip, which no earlier test takes (their
+    """k_events_table.h:158, `base += gridDim.x * CHUNK_WG` of evtab_for_rows under k_evtab_reduce (:167): its second trip, which no earlier test takes (their
     batches hold a few thousand events, one trip covers 32 * CUs * 256).  Behind cap the batch has dwells of 1, 63, 64, 65 and above 128
     and a wavefront with both kinds, so evtab_take's lane loop and its ballot / shuffle loop both run there, in one wavefront too; the
-    last wavefront is partly empty (n_events is no multiple of 64), and `if (!have) continue` at line 151 is met on the second trip.  All
+    last wavefront is partly empty (n_events is no multiple of 64), and `if (have)` at line 170 is false on the second trip.  All
     twelve columns: the sample-derived ones against events_vec over the fetched signal and dwells, the places against np.repeat / cumsum
     of the dwells, k-mer, segment and level against events_ref on the first read, the last and the one that straddles cap"""
     d = _Grid.get()
@@ -355,10 +355,10 @@ def test_events_behind_the_first_trip_of_the_grid(norm):
 @pytest.mark.gpu
 @pytest.mark.parametrize("norm", ["pa", "medmad"])
 def test_detected_rows_behind_the_first_trip_of_the_grid(norm):
-    """k_detect.h:184, `base += gridDim.x * CHUNK_WG` of k_detect_rows: its second trip, which no earlier test takes (their tables hold a
+    """k_events_table.h:158, `base += gridDim.x * CHUNK_WG` of evtab_for_rows under k_detect_rows (k_detect.h:183): its second trip, which no earlier test takes (their tables hold a
     few hundred thousand rows, one trip covers 32 * CUs * 256).  Behind cap the table has rows of 2, 63, 64, 65 and more than 128
     samples that start at odd and at even samples of the slab, and a wavefront with both kinds, so evtab_take's lane loop and its
-    ballot / shuffle loop both run there; the last wavefront is partly empty, and `if (!have) continue` at line 190 is met on the second
+    ballot / shuffle loop both run there; the last wavefront is partly empty, and `if (!have) return` at k_detect.h:187 is met on the second
     trip.  det_off of the plan call and all twelve outputs against detect_vec, which the test above pins to detect_ref"""
     d = _DetectGrid.get()
     b, cap = d["b"], d["cap"]
@@ -445,8 +445,8 @@ def _laid_over_a_span(lens, k, width, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("norm", ["pa", "medmad"])
 def test_pileup_behind_the_first_trip_of_the_grid(norm):
-    """k_pileup.h:33, `base += gridDim.x * CHUNK_WG` of k_pileup: its second trip, with the two ballots of line 63 and the `continue`
-    of line 68 on it, which no earlier test takes.  The drawn-dwell batch of the event test under a caller's origin that lays 600 reads
+    """k_events_table.h:158, `base += gridDim.x * CHUNK_WG` of evtab_for_rows under k_pileup (k_pileup.h:32): its second trip, with the
+    two ballots of k_pileup.h:60 and the `return` of line 65 on it, which no earlier test takes.  The drawn-dwell batch of the event test under a caller's origin that lays 600 reads
     over some 9000 keys, half of them backwards (a few hundred adds per key), by position with a window that cuts the span at both ends
     and by pore-table row with a window over half the rows: events behind cap are counted and are outside, so evtab_take gets lanes that
     are taken and lanes that are not next to long events there.  All six outputs against pileup_ref over the batch's event table (which
@@ -487,7 +487,7 @@ def test_pileup_behind_the_first_trip_of_the_grid(norm):
 
 @pytest.mark.gpu
 def test_pileup_keys_beyond_32_bits_and_below_zero():
-    """k_pileup.h:50 and 60, `key = pr.key0 + step * j` and the window comparison, and :69, `key - U.lo`, with keys that need more than
+    """k_pileup.h:47 and 57, `key = pr.key0 + step * j` and the window comparison, and :66, `key - U.lo`, with keys that need more than
     32 bits (hg38 laid end to end passes 2^31 at chr13) and with negative ones: every earlier key is below 30 000.  A caller's origin is
     shifted by 2^31 - 150, 2^32 - 150, 2^40 + 7, -150 and -2^33 - 150 together with a window that cuts reads at both ends and straddles the
     power of two (or 0): the six arrays of both strand planes and (counted, outside) must be those of the unshifted call, which is
@@ -614,7 +614,7 @@ def test_the_sampler_origin_on_four_contigs_and_both_strands():
 @pytest.mark.gpu
 @pytest.mark.parametrize("dwell", [LANE_MAX + 1, 5000])
 def test_long_events_beside_lanes_that_are_not_taken(dwell):
-    """k_pileup.h:62, `evtab_take(W, inside && ..., ...)` with `take` false in some lanes of a wavefront whose other lanes hold events
+    """k_pileup.h:59, `evtab_take(W, inside && ..., ...)` with `take` false in some lanes of a wavefront whose other lanes hold events
     longer than EVT_LANE_MAX: evtab_take's ballot (k_events_table.h:81) then has holes, and the lanes that are not taken still load and
     shuffle for their neighbours.  The earlier constant-dwell test has all 76 events inside the window.  Dwells of 65 and 5000; by row with
     a window over a scattered subset of the events, and by position with a window that takes events 10 .. 40 of the 70-event read; the
