@@ -681,7 +681,7 @@ class Batch:
                     label_len=new((nc,), torch.int32) if labels else None,
                     chunk_read=new((nc,), torch.int32), chunk_start=new((nc,), torch.int64),
                     med2=torch.zeros(self.n_reads, dtype=torch.int32, device=dev), mad4=torch.zeros(self.n_reads, dtype=torch.int32, device=dev))
-        if nc:
+        if self.n_reads:                                    # (also for a plan without chunks: med2 / mad4 are written for every read)
             call("sqg_batch_chunks", CChunkOut, ch.signal, ch.labels, ch.label_len, ch.chunk_read, ch.chunk_start, ch.med2, ch.mad4)
         return ch
 

@@ -61,29 +61,62 @@ JOBS = {
 }
 
 
+# what the consumer calls of a setup are asked for: an attribute of the setup each, these being the defaults (the jobs of JOBS run under them)
+CFGS = dict(
+    chunk=CHUNK, chunk_settings=CHUNK_SETTINGS,
+    site_geometries=SITE_GEOMETRIES, focus=None, site_ctx=(21, 10),     # focus None: (k + 1) // 2; site_ctx: (ctx_len, ctx_before)
+    event_settings=EVENT_SETTINGS,                          # the first one is the table the aligner's references read: ("pa", False)
+    detect_b=DETECT_B,
+    align_detected=None,                                    # None: the call passes no cfg and the reference takes ALIGN_DEFAULT
+    align_rows=("detect A",),                               # the detectors whose rows are aligned: "align detected", "align detected B"
+    align_truth=ALIGN_TRUTH,
+    pile_kmer=False,                                        # True: pile_cfgs has a by="kmer" pileup without a prefix too
+)
+
+
 class Setup:
     """what a job's contexts are created with, and what the references need to know of them"""
 
     def __init__(self, name, extra_flags=0):
         j = JOBS[name]
+        prof, fl = profiles.get_profile(j["profile"])
+        flags = fl | j.get("flags", 0) | (profiles.SQ_METH if j.get("meth") else 0) | extra_flags
+        self._set(name, j, prof, flags, j.get("k") or profiles.default_kmer_size(flags), 0, {})
+
+    @classmethod
+    def of(cls, name, prof, flags, k, salt, T, batches, amp_noise=1.0, seed=SEED, **cfgs):
+        """a setup from explicit values instead of a JOBS name: one plain context (G = 1) of T workers over the profile object prof, the
+        whole flag word (the profile's own bits and SQ_METH included), k-mers of k bases, the synthetic model of that salt, the staged
+        reads `batches` (a list of lists of bytes), and any of CFGS by keyword"""
+        su = cls.__new__(cls)
+        su._set(name, dict(kind="staged", T=T, G=1, reads_seed=seed), prof, flags, k, salt, cfgs)
+        su.batches, su.amp_noise, su.seed = [list(bt) for bt in batches], amp_noise, seed
+        return su
+
+    def _set(self, name, j, prof, flags, k, salt, cfgs):
         self.name, self.job = name, j
-        self.prof, fl = profiles.get_profile(j["profile"])
-        self.meth = bool(j.get("meth"))
-        self.flags = fl | j.get("flags", 0) | (profiles.SQ_METH if self.meth else 0) | extra_flags
-        self.k = j.get("k") or profiles.default_kmer_size(self.flags)
-        self.mean, self.stdv = model.synthetic_model(self.k, meth=self.meth)
+        self.prof, self.flags, self.k = prof, flags, k
+        self.meth = bool(flags & profiles.SQ_METH)
+        self.mean, self.stdv = model.synthetic_model(self.k, salt=salt, meth=self.meth)
         self.rna, self.prefix = bool(self.flags & profiles.SQ_RNA), bool(self.flags & profiles.SQ_PREFIX)
         self.sps = int(self.prof.dwell_mean)
         self.T, self.G = j["T"], j["G"]
         self.sampled = j["kind"] in ("range_sampled", "worker_sampled")
         self.by_worker = j["kind"] in ("worker_staged", "worker_sampled")
         self.sites = not self.rna and not self.prefix
-        self.focus = (self.k + 1) // 2
         self.n_rows = self.T * len(self.mean)
         self.contigs = self.names = None
+        self.batches, self.amp_noise, self.seed = None, 1.0, SEED
+        assert set(cfgs) <= set(CFGS), sorted(set(cfgs) - set(CFGS))
+        for key, default in CFGS.items():
+            setattr(self, key, cfgs.get(key, default))
+        if self.focus is None:
+            self.focus = (self.k + 1) // 2
+        assert tuple(self.event_settings[0]) == ("pa", False) and set(self.align_rows) <= {"detect A", "detect B"}
 
     def generator(self, mode=api.MODE_CERTIFIED, worker_lo=0, worker_hi=None):
-        g = api.SignalGenerator(self.prof, self.flags, self.k, self.mean, self.stdv, SEED, num_workers=self.T, mode=mode, worker_lo=worker_lo, worker_hi=worker_hi)
+        g = api.SignalGenerator(self.prof, self.flags, self.k, self.mean, self.stdv, self.seed, num_workers=self.T, amp_noise=self.amp_noise, mode=mode,
+                                worker_lo=worker_lo, worker_hi=worker_hi)
         if self.sampled:
             self.oracle_job()                               # (the contigs as the oracle loaded them)
             g.load_genome(self.contigs, self.job["rlen"], self.job.get("sample", api.SAMPLE_DNA))
@@ -94,6 +127,8 @@ class Setup:
     # ---- the job on the CPU
     def staged_reads(self):
         j = self.job
+        if self.batches is not None:                        # a setup made by Setup.of: the reads it was given
+            return self.batches
         rng = np.random.default_rng(j["reads_seed"])
         out = [[bytes(rng.choice(list(j["letters"]), int(m)).astype(np.uint8)) for m in rng.integers(*j["lengths"], nb)] for nb in j["sizes"]]
         for bi, i, m in j.get("short", ()):                 # reads shorter than a k-mer: the first m bases of the read drawn at that place
@@ -111,7 +146,7 @@ class Setup:
             self.contigs, self.names = _ORACLE[(self.name, self.flags)][1:]
             return _ORACLE[(self.name, self.flags)][0]
         j = self.job
-        orac = orc.Oracle(self.prof, self.flags, self.k, self.mean, self.stdv, SEED, num_workers=self.T, rlen=j.get("rlen", 10000))
+        orac = orc.Oracle(self.prof, self.flags, self.k, self.mean, self.stdv, self.seed, num_workers=self.T, rlen=j.get("rlen", 10000), amp_noise=self.amp_noise)
         out = []
         if self.sampled:
             ref = orac.load_ref(j["fasta"], None, MFREQ_DENSE if self.meth else None)
@@ -158,9 +193,13 @@ class Setup:
         lo, hi = self.window()
         out["ref_split"] = (dict(by="ref", split=("strand", "meth") if self.meth else ("strand",), lo=lo, hi=hi), "pa", False)
         keys = np.sort(np.concatenate([self.keys(o, np.arange(len(o["reads"]))) for o in self.oracle_job()]))
-        out["ref_window"] = (dict(by="ref", lo=int(keys[len(keys) // 4]) + 1, hi=int(keys[3 * len(keys) // 4])), "medmad", False)
+        if len(keys):                                       # (a job of JOBS always has some; a drawn one may hold nothing but reads without a step)
+            lo = int(keys[len(keys) // 4]) + 1
+            out["ref_window"] = (dict(by="ref", lo=lo, hi=max(int(keys[3 * len(keys) // 4]), lo + 1)), "medmad", False)
         if self.prefix:
             out["kmer_segs"] = (dict(by="kmer", segs=(0, 1, 2, 3)), "medmad", True)
+        elif self.pile_kmer:
+            out["kmer"] = (dict(by="kmer"), "medmad", True)
         return out
 
     def keys(self, o, idx):
@@ -175,8 +214,14 @@ class Setup:
         preset = "rna" if self.rna else "dna"
         out = {"detect A": (DT.RNA if self.rna else DT.DNA, preset, "pa", False)}
         if not threaded:
-            out["detect B"] = (DETECT_B, DETECT_B, "medmad", True)
+            out["detect B"] = (self.detect_b, self.detect_b, "medmad", True)
         return out
+
+    def align_settings(self, threaded=False):
+        """the detector's name -> (the align group of its rows, the cfg the call is given, the cfg the reference takes)"""
+        cfg = self.align_detected
+        names = {"detect A": "align detected", "detect B": "align detected B"}
+        return {d: (names[d], cfg, ALIGN_DEFAULT if cfg is None else cfg) for d in self.detect_settings(threaded) if d in self.align_rows}
 
     def expected_detect_align(self, reads, ev, threaded=False, seen=None, plain=False):
         """the groups of sqg_batch_detect and sqg_batch_align: detect_ref and align_ref over the reads and over ev, events_ref's table of
@@ -195,9 +240,11 @@ class Setup:
                 seen[name] = info
             out[name] = dict(off=w["det_off"], read=w["dt_read"], rows={key: w[key] for key in DT.PER_ROW if key != "dt_read"},
                              per_read=dict(med2=w["med2"], mad4=w["mad4"]))
-        w, ev_off = det["detect A"], ev["ev_off"]
-        a = AL.batch(w["det_off"], w["sum"], w["dt_len"], ev_off, ev["level_raw"], rna, ALIGN_DEFAULT, one=banded)
-        out["align detected"] = dict(off=w["det_off"], read=w["dt_read"], rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
+        ev_off = ev["ev_off"]
+        for d, (name, _, cfg) in self.align_settings(threaded).items():
+            w = det[d]
+            a = AL.batch(w["det_off"], w["sum"], w["dt_len"], ev_off, ev["level_raw"], rna, cfg, one=banded)
+            out[name] = dict(off=w["det_off"], read=w["dt_read"], rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
         if not threaded:
             def both(q, lv, cfg):                           # a read of at most 32 events: the full matrix as well, what is compared is held to both
                 js, cost, edge = banded(q, lv, cfg)
@@ -206,17 +253,18 @@ class Setup:
                     assert fj.tolist() == js.tolist() and (fc, fe) == (cost, edge), "align_ref's two statements differ"
                 return js, cost, edge
             idx = stored_order(ev_off, rna)
-            a = AL.batch(ev_off, ev["sum"][idx], ev["ev_len"][idx], ev_off, ev["level_raw"], rna, ALIGN_TRUTH, one=both)
+            a = AL.batch(ev_off, ev["sum"][idx], ev["ev_len"][idx], ev_off, ev["level_raw"], rna, self.align_truth, one=both)
             out["align truth"] = dict(off=ev_off, read=ev["ev_read"], rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
         return out
 
     # ---- the references, as groups: name -> dict(off [n_reads + 1], read [rows], rows {key: [rows, ...]}, per_read {key: [n_reads]})
-    def expected(self, reads, threaded=False):
+    def expected(self, reads, threaded=False, seen=None):
+        """seen: as in expected_detect_align"""
         p, k, rna, meth, prefix, sps, mean = self.prof, self.k, self.rna, self.meth, self.prefix, self.sps, self.mean
-        L, St, W = CHUNK
+        L, St, W = self.chunk
         n = len(reads)
         out = {}
-        for dtype, norm in CHUNK_SETTINGS[:1] if threaded else CHUNK_SETTINGS:
+        for dtype, norm in self.chunk_settings[:1] if threaded else self.chunk_settings:
             fdt = np.float16 if dtype == "f16" else np.float32
             if n == 0:
                 w = dict(signal=np.zeros((0, L), fdt), labels=np.zeros((0, W), np.uint8), label_len=np.zeros(0, np.int32), chunk_start=np.zeros(0, np.int64),
@@ -234,16 +282,16 @@ class Setup:
                 assert n == 0 or np.array_equal(t["chunk_off"], w["chunk_off"])
                 out[f"targets {dtype} {norm}"] = dict(off=w["chunk_off"], read=w["chunk_read"], rows={key: t[key] for key in ("clean", "clean_raw", "moves", "kmer")}, per_read={})
         if self.sites:
-            for Lw, before in SITE_GEOMETRIES[:1] if threaded else SITE_GEOMETRIES:
-                w = S.batch_sites(reads, k, meth, S.Cfg(Lw, before, self.focus, 21, 10, "f16", "medmad"), p.range, p.digitisation)
+            for Lw, before in self.site_geometries[:1] if threaded else self.site_geometries:
+                w = S.batch_sites(reads, k, meth, S.Cfg(Lw, before, self.focus, *self.site_ctx, "f16", "medmad"), p.range, p.digitisation)
                 out[f"sites {Lw}"] = dict(off=w["site_off"], read=w["site_read"], rows={key: w[key] for key in S.KEYS if key != "site_read"},
                                           per_read=dict(med2=w["med2"], mad4=w["mad4"]))
-        for norm, trim in EVENT_SETTINGS[:1] if threaded else EVENT_SETTINGS:
+        for norm, trim in self.event_settings[:1] if threaded else self.event_settings:
             w = EV.batch_events(reads, mean, k, rna, meth, prefix, sps, norm, trim, p.range, p.digitisation)
             out[f"events {norm} {int(trim)}"] = dict(off=w["ev_off"], read=w["ev_read"], rows={key: w[key] for key in EV.PER_EVENT if key != "ev_read"},
                                                     per_read=dict(med2=w["med2"], mad4=w["mad4"]))
-            if (norm, trim) == EVENT_SETTINGS[0]:
-                out.update(self.expected_detect_align(reads, w, threaded))
+            if (norm, trim) == tuple(self.event_settings[0]):
+                out.update(self.expected_detect_align(reads, w, threaded, seen))
         if prefix and not threaded:
             seg, shift = SR.batch_segments(reads, k, rna, prefix, sps)
             out["segments"] = dict(off=np.arange(n + 1, dtype=np.int64), read=np.arange(n, dtype=np.int32), rows=dict(seg=seg, shift=shift), per_read={})
@@ -251,8 +299,8 @@ class Setup:
 
     def expected_sites(self, reads):
         """sites_ref at the first geometry: window 256, 128 samples in front of the anchor event"""
-        Lw, before = SITE_GEOMETRIES[0]
-        return S.batch_sites(reads, self.k, self.meth, S.Cfg(Lw, before, self.focus, 21, 10, "f16", "medmad"), self.prof.range, self.prof.digitisation)
+        Lw, before = self.site_geometries[0]
+        return S.batch_sites(reads, self.k, self.meth, S.Cfg(Lw, before, self.focus, *self.site_ctx, "f16", "medmad"), self.prof.range, self.prof.digitisation)
 
     def pileup_table(self, reads, norm, trim, need_kmer):
         """the per-event columns pileup_ref takes: events_ref's, or -- where neither the key nor a split needs k-mer and segment -- the
@@ -283,52 +331,104 @@ class Setup:
         return into, counted, outside
 
     # ---- the consumer calls of a batch, as the same groups
-    def consume(self, b, threaded=False):
-        L, St, W = CHUNK
+    def consume(self, b, threaded=False, order=None, extra=()):
+        """extra: further steps (callables that take the dict of groups), behind the listed ones.  order: a permutation of
+        range(len(self.consume_steps(b, threaded)) + len(extra)) -- the steps run in that order instead of the listed one.
+        The aligner takes a detector's own tensors: if its step comes first, the detector's step runs there, in front of it, and not
+        again.  What is returned does not depend on the order"""
+        steps = self.consume_steps(b, threaded) + [(None, step) for step in extra]
+        out, ran = {}, set()
+        for i in range(len(steps)) if order is None else order:
+            need, step = steps[i]
+            for j in ([] if need is None else [need]) + [i]:
+                if j not in ran:
+                    ran.add(j)
+                    steps[j][1](out)
+        assert len(ran) == len(steps)
+        return out
+
+    def consume_steps(self, b, threaded=False):
+        """the calls of consume() on batch b in the listed order: [(the index of the step that must have run before, or None, the step)];
+        a step takes the dict of groups and adds its own"""
+        L, St, W = self.chunk
         trim = self.prefix
-        out = {}
         cpu = _host
-        for dtype, norm in CHUNK_SETTINGS[:1] if threaded else CHUNK_SETTINGS:
-            ch = b.chunks(L, St, W, dtype=dtype, norm=norm, trim=trim)
-            plan, nc = b.chunk_plan(L, St, trim=trim)
-            assert nc == ch.n_chunks == len(ch.chunk_read) and plan[-1] == nc
-            out[f"chunks {dtype} {norm}"] = dict(off=ch.chunk_off, plan=plan, read=cpu(ch.chunk_read), rows={key: cpu(getattr(ch, key)) for key in ("signal", "labels", "label_len", "chunk_start")},
-                                                 per_read=dict(med2=cpu(ch.med2), mad4=cpu(ch.mad4)))
-            if not threaded:
-                tg = b.chunk_targets(L, St, dtype=dtype, norm=norm, clean=True, clean_raw=True, moves=True, kmer=True, trim=trim)
-                assert tg.n_chunks == nc
-                out[f"targets {dtype} {norm}"] = dict(off=tg.chunk_off, read=cpu(ch.chunk_read), rows={key: cpu(getattr(tg, key), key) for key in ("clean", "clean_raw", "moves", "kmer")}, per_read={})
-        if self.sites:
-            for Lw, before in SITE_GEOMETRIES[:1] if threaded else SITE_GEOMETRIES:
-                st = b.sites(Lw, before, self.focus, 21, 10, dtype="f16", norm="medmad")
+        steps, kept = [], {}
+
+        def chunks(dtype, norm):
+            def step(out):
+                ch = b.chunks(L, St, W, dtype=dtype, norm=norm, trim=trim)
+                plan, nc = b.chunk_plan(L, St, trim=trim)
+                assert nc == ch.n_chunks == len(ch.chunk_read) and plan[-1] == nc
+                out[f"chunks {dtype} {norm}"] = dict(off=ch.chunk_off, plan=plan, read=cpu(ch.chunk_read), rows={key: cpu(getattr(ch, key)) for key in ("signal", "labels", "label_len", "chunk_start")},
+                                                     per_read=dict(med2=cpu(ch.med2), mad4=cpu(ch.mad4)))
+                if not threaded:
+                    tg = b.chunk_targets(L, St, dtype=dtype, norm=norm, clean=True, clean_raw=True, moves=True, kmer=True, trim=trim)
+                    assert tg.n_chunks == nc
+                    out[f"targets {dtype} {norm}"] = dict(off=tg.chunk_off, read=cpu(ch.chunk_read), rows={key: cpu(getattr(tg, key), key) for key in ("clean", "clean_raw", "moves", "kmer")}, per_read={})
+            return step
+
+        def sites(Lw, before):
+            def step(out):
+                st = b.sites(Lw, before, self.focus, *self.site_ctx, dtype="f16", norm="medmad")
                 plan, ns = b.site_plan(Lw, before, self.focus)
                 assert ns == st.n_sites
                 out[f"sites {Lw}"] = dict(off=st.site_off, plan=plan, read=cpu(st.site_read), rows={key: cpu(getattr(st, key)) for key in S.KEYS if key != "site_read"},
                                           per_read=dict(med2=cpu(st.med2), mad4=cpu(st.mad4)))
-        for norm, tr in EVENT_SETTINGS[:1] if threaded else EVENT_SETTINGS:
-            ev = b.events(norm, tr)
-            assert ev.n_events == b.n_events
-            out[f"events {norm} {int(tr)}"] = dict(off=b.ev_off, read=cpu(ev.ev_read), rows={key: cpu(getattr(ev, key), key) for key in EV.PER_EVENT if key != "ev_read"},
-                                                  per_read=dict(med2=cpu(ev.med2), mad4=cpu(ev.mad4)))
-        for name, (_, cfg, norm, tr) in self.detect_settings(threaded).items():
-            dt = b.detect(cfg, norm, tr)
-            plan, nr = b.detect_plan(cfg)
-            assert nr == dt.n_rows == len(dt.dt_read) and plan[-1] == nr
-            out[name] = dict(off=dt.det_off, plan=plan, read=cpu(dt.dt_read), rows={key: cpu(getattr(dt, key)) for key in DT.PER_ROW if key != "dt_read"},
-                             per_read=dict(med2=cpu(dt.med2), mad4=cpu(dt.mad4)))
-            if name == "detect A":                          # the tensors handed on as they are, under SQG_ALIGN_DEFAULT
-                al = b.align(dt.det_off, dt.sum, dt.dt_len)
-                assert al.n_rows == nr
-                out["align detected"] = dict(off=al.row_off, read=cpu(dt.dt_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
-        if not threaded:                                    # the true table's own rows in stored-sample order: row_off is ev_off
+            return step
+
+        def events(norm, tr):
+            def step(out):
+                ev = b.events(norm, tr)
+                assert ev.n_events == b.n_events
+                out[f"events {norm} {int(tr)}"] = dict(off=b.ev_off, read=cpu(ev.ev_read), rows={key: cpu(getattr(ev, key), key) for key in EV.PER_EVENT if key != "ev_read"},
+                                                      per_read=dict(med2=cpu(ev.med2), mad4=cpu(ev.mad4)))
+            return step
+
+        def detect(name, cfg, norm, tr):
+            def step(out):
+                dt = kept[name] = b.detect(cfg, norm, tr)
+                plan, nr = b.detect_plan(cfg)
+                assert nr == dt.n_rows == len(dt.dt_read) and plan[-1] == nr
+                out[name] = dict(off=dt.det_off, plan=plan, read=cpu(dt.dt_read), rows={key: cpu(getattr(dt, key)) for key in DT.PER_ROW if key != "dt_read"},
+                                 per_read=dict(med2=cpu(dt.med2), mad4=cpu(dt.mad4)))
+            return step
+
+        def align_detected(name, group, cfg):               # the tensors handed on as they are; cfg None: under SQG_ALIGN_DEFAULT
+            def step(out):
+                dt = kept[name]
+                al = b.align(dt.det_off, dt.sum, dt.dt_len) if cfg is None else b.align(dt.det_off, dt.sum, dt.dt_len, cfg)
+                assert al.n_rows == dt.n_rows
+                out[group] = dict(off=al.row_off, read=cpu(dt.dt_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
+            return step
+
+        def align_truth(out):                               # the true table's own rows in stored-sample order: row_off is ev_off
             ev = b.events(outputs=("ev_read", "sum", "ev_len"))
             idx = torch.from_numpy(stored_order(b.ev_off, self.rna)).to(ev.sum.device)
-            al = b.align(b.ev_off, ev.sum[idx].contiguous(), ev.ev_len[idx].contiguous(), ALIGN_TRUTH)
+            al = b.align(b.ev_off, ev.sum[idx].contiguous(), ev.ev_len[idx].contiguous(), self.align_truth)
             out["align truth"] = dict(off=al.row_off, read=cpu(ev.ev_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
-        if self.prefix and not threaded:
+
+        def segments(out):
             seg, shift = b.segments()
             out["segments"] = dict(off=np.arange(b.n_reads + 1, dtype=np.int64), read=np.arange(b.n_reads, dtype=np.int32), rows=dict(seg=cpu(seg), shift=cpu(shift)), per_read={})
-        return out
+
+        for dtype, norm in self.chunk_settings[:1] if threaded else self.chunk_settings:
+            steps.append((None, chunks(dtype, norm)))
+        if self.sites:
+            for Lw, before in self.site_geometries[:1] if threaded else self.site_geometries:
+                steps.append((None, sites(Lw, before)))
+        for norm, tr in self.event_settings[:1] if threaded else self.event_settings:
+            steps.append((None, events(norm, tr)))
+        aligned = self.align_settings(threaded)
+        for name, (_, cfg, norm, tr) in self.detect_settings(threaded).items():
+            steps.append((None, detect(name, cfg, norm, tr)))
+            if name in aligned:
+                steps.append((len(steps) - 1, align_detected(name, aligned[name][0], aligned[name][1])))
+        if not threaded:
+            steps.append((None, align_truth))
+        if self.prefix and not threaded:
+            steps.append((None, segments))
+        return steps
 
     def origin(self, o, idx):
         """what Batch.pileup takes as origin= for reads idx of the oracle's batch o: nothing for a sampled batch -- the rank derives the keys

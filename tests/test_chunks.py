@@ -217,6 +217,30 @@ def test_degenerate_reads():
 
 
 @pytest.mark.gpu
+def test_statistics_of_a_batch_without_a_chunk():
+    """med2 and mad4 are written for every read: also when no read of the batch has a chunk -- reads shorter than k, and reads with fewer
+    samples than a chunk --, Batch.chunks makes the call and returns them, not zeros, beside tensors of no rows"""
+    prof, fl = profiles.get_profile("dna-r9-prom")
+    k = profiles.default_kmer_size(fl)
+    mean, stdv = model.synthetic_model(k)
+    seqs = [b"ACG", b"ACGTACGTAC", b"T", b"GATTACAGATT"]
+    orac = orc.Oracle(prof, fl, k, mean, stdv, 42, num_workers=1)
+    want_reads = [dict(sig=w.sig, ss=w.ss, seq=s, offset=w.offset) for w, s in zip(orac.run_batch_seqs(seqs), seqs)]
+    orac.close()
+    gen = api.SignalGenerator(prof, fl, k, mean, stdv, 42, num_workers=1)
+    b = gen.submit(seqs)
+    L = 2048
+    assert all(0 < len(w["sig"]) < L for w in want_reads)
+    for dtype, norm in ALL_SETTINGS:
+        want = R.batch_chunks(want_reads, k, False, False, L, L, 16, dtype, norm, prof.range, prof.digitisation)
+        ch = b.chunks(L, L, 16, dtype=dtype, norm=norm)
+        assert ch.n_chunks == 0 and want["chunk_off"].tolist() == [0] * 5 and tuple(ch.signal.shape) == (0, L) and tuple(ch.labels.shape) == (0, 16)
+        assert (want["med2"] != 0).all() and (want["mad4"] != 0).all()
+        _assert_equal(ch, want, f"no chunk, {dtype} {norm}")
+    b.free(); gen.close()
+
+
+@pytest.mark.gpu
 def test_codes_wider_than_the_lds_histogram():
     """a profile whose range is so small that a read's codes span tens of thousands of ADC values (and wrap the int16): the generic path,
     expected values from chunks_ref over the oracle's signal"""
