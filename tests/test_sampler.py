@@ -21,7 +21,27 @@ def _contigs(ref):
     return [bytes(ref.seqs[i][:ref.lengths[i]]) for i in range(ref.num_ref)]
 
 
-def _run(profile, k, fasta, T, batches, rlen, oflags=0, sflags=0, mode=api.SAMPLE_DNA, trans_count=None, seed=42, meth_freq=None):
+def _compare(b, want):
+    """a sampled batch against the oracle's reads of it, read for read and bit for bit: coordinates, sequence, signal, dwells, offset and
+    median_before"""
+    assert b.n_reads == len(want)
+    s = b.sampled
+    seqs = b.reads()
+    sig, dw = b.signal(), b.dwell()
+    for i, w in enumerate(want):
+        assert (s["ref_idx"][i], s["ref_pos"][i], s["rlen"][i], chr(s["strand"][i])) == \
+               (w.ref_idx, w.ref_pos_st, w.rlen, w.strand), f"read {i}"
+        assert s["ref_len"][i] == w.ref_len
+        assert seqs[i] == w.seq, f"read {i}: sequence differs"
+        np.testing.assert_array_equal(sig[b.sig_off[i]:b.sig_off[i + 1]], w.sig, err_msg=f"read {i}")
+        np.testing.assert_array_equal(dw[b.ev_off[i]:b.ev_off[i + 1]], w.ss)
+        assert b.offset[i] == w.offset and b.median_before[i] == w.median_before, f"read {i}: offset / median_before"
+
+
+def _run(profile, k, fasta, T, batches, rlen, oflags=0, sflags=0, mode=api.SAMPLE_DNA, trans_count=None, seed=42, meth_freq=None, trans_scale=None,
+         reads_out=None):
+    """trans_scale: the oracle's cumulative abundances are scaled in place so that the last one is trans_scale, and the device gets the same
+    table; reads_out: a list that takes the oracle's reads, one list per batch"""
     prof, fl = profiles.get_profile(profile)
     if meth_freq:
         sflags |= profiles.SQ_METH
@@ -30,6 +50,9 @@ def _run(profile, k, fasta, T, batches, rlen, oflags=0, sflags=0, mode=api.SAMPL
     ref = orac.load_ref(fasta, trans_count, meth_freq)
     trans = None
     if trans_count:
+        if trans_scale is not None:
+            view = np.ctypeslib.as_array(ref.trans_csum, shape=(ref.trans_n,))
+            view *= np.float32(trans_scale) / view[-1]
         trans = (np.ctypeslib.as_array(ref.trans_csum, shape=(ref.trans_n,)).copy(),
                  np.ctypeslib.as_array(ref.trans_idx, shape=(ref.trans_n,)).copy())
     gen = api.SignalGenerator(prof, fl | sflags, k, mean, stdv, seed, num_workers=T, mode=api.MODE_CERTIFIED)
@@ -39,17 +62,10 @@ def _run(profile, k, fasta, T, batches, rlen, oflags=0, sflags=0, mode=api.SAMPL
     total = 0
     for nb in batches:
         want = orac.run_batch(nb)
+        if reads_out is not None:
+            reads_out.append(want)
         b = gen.sample(nb).run().wait()
-        s = b.sampled
-        seqs = b.reads()
-        sig, dw = b.signal(), b.dwell()
-        for i, w in enumerate(want):
-            assert (s["ref_idx"][i], s["ref_pos"][i], s["rlen"][i], chr(s["strand"][i])) == \
-                   (w.ref_idx, w.ref_pos_st, w.rlen, w.strand), f"read {i}"
-            assert s["ref_len"][i] == w.ref_len
-            assert seqs[i] == w.seq, f"read {i}: sequence differs"
-            np.testing.assert_array_equal(sig[b.sig_off[i]:b.sig_off[i + 1]], w.sig, err_msg=f"read {i}")
-            np.testing.assert_array_equal(dw[b.ev_off[i]:b.ev_off[i + 1]], w.ss)
+        _compare(b, want)
         total += nb
         b.free()
     gen.close(); orac.close()
