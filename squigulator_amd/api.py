@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h and include/sqg_align.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h and include/sqg_collapse.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -207,6 +207,28 @@ class CAlignOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ALIGN_OUTPUTS]
 
 
+# include/sqg_collapse.h: bound the same way
+EXPORTS_COLLAPSE = ("sqg_batch_collapse", "sqg_batch_pileup_rows")
+COLLAPSE_INPUTS = ("ev", "sum", "sumsq", "len")
+COLLAPSE_OUTPUTS = ("ob_rows", "ob_len", "ob_sum", "ob_sumsq", "mean", "sd", "rd_dropped")
+
+
+class CCollapseCfg(C.Structure):
+    _fields_ = [("norm", C.c_uint32), ("trim", C.c_int32)]
+
+
+class CCollapseIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in COLLAPSE_INPUTS]
+
+
+class CCollapseOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in COLLAPSE_OUTPUTS]
+
+
+class CPileupRowsStat(C.Structure):
+    _fields_ = [("counted", C.c_int64), ("outside", C.c_int64), ("unseen", C.c_int64), ("dropped", C.c_int64)]
+
+
 class Pileup:
     """What SignalGenerator.new_pileup() returns: the cfg of a pileup and its sums, torch tensors [planes, hi - lo] on the context's device
     that Batch.pileup() adds to (include/sqg_pileup.h says what they hold); those not asked for are None"""
@@ -234,6 +256,8 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
     (EXPORTS_DETECT, {"sqg_detect_plan": (CDetectCfg,) + _PLAN, "sqg_batch_detect": (CDetectCfg, CDetectOut)}),
     (EXPORTS_ALIGN, {"sqg_batch_align": (CAlignCfg, C.c_int64, CAlignIn, CAlignOut)}),
+    (EXPORTS_COLLAPSE, {"sqg_batch_collapse": (CCollapseCfg, C.c_int64, CCollapseIn, CCollapseOut),
+                        "sqg_batch_pileup_rows": (CPileupCfg, COrigin, C.c_int64, CCollapseIn, CPileupOut, CPileupRowsStat)}),
 )
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
@@ -823,18 +847,82 @@ class Batch:
         return self._table("sqg_batch_align", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CAlignOut, ALIGN_OUTPUTS, shapes, want,
                            n_rows=nr, row_off=off)
 
+    def _rows(self, who, row_off, ev, sum, sumsq, len):       # noqa: A002
+        """the rows of collapse() / pileup_rows(), checked as align() checks its own: (row_off as int64, n_rows, the C struct of addresses,
+        what keeps them alive)"""
+        import torch
+        off = np.ascontiguousarray(row_off, np.int64)
+        if off.shape != (self.n_reads + 1,):
+            raise SqgError(-1, who, f"row_off must have {self.n_reads + 1} elements")
+        nr = max(int(off[-1]), 0)
+        dev = torch.device("cuda", self.gen.device)
+        for name, t, dt in (("ev", ev, torch.int64), ("sum", sum, torch.int64), ("sumsq", sumsq, torch.int64), ("len", len, torch.int32)):
+            if t is None and name == "sumsq":
+                continue                                        # (the library says which outputs need it)
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
+                raise SqgError(-1, who, f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
+        keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
+        cin = CCollapseIn(*(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in (ev, sum, sumsq, len)))
+        return off, nr, cin, keep
+
+    def collapse(self, row_off, ev, sum, sumsq, len, norm="pa", trim: bool = False, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
+        """The observed event table: the rows [row_off[r], row_off[r+1]) of sum / sumsq / len -- Batch.detect()'s det_off, sum, sumsq and
+        dt_len, or any other -- summed per row of Batch.events() they are assigned to by ev -- Batch.align()'s al_ev, the detector's
+        true_ev, or the caller's own -- on the device (sqg_batch_collapse, include/sqg_collapse.h).  A row whose ev is not an event of its
+        own read is dropped.  row_off: [n_reads+1] integers on the host; ev, sum, sumsq (int64) and len (int32): torch tensors of
+        row_off[-1] elements on the context's device; sumsq may be None when neither ob_sumsq nor sd is wanted.  torch tensors [n_events]:
+        ob_rows (uint32 bit patterns in an int32 tensor), ob_len, ob_sum, ob_sumsq (int64), mean, sd (float32: the event table's formulas
+        on the sums, normalised by norm, 0 for an event without a sample); rd_dropped [n_reads] (int32).  outputs: the names wanted
+        (default all); the others are None."""
+        import torch
+        _need(self.gen.L, "sqg_batch_collapse", "sqg_collapse.h", "collapse")
+        nm, = _enum("collapse", norm=norm)
+        want = _want(outputs, COLLAPSE_OUTPUTS, "collapse")
+        off, nr, cin, keep = self._rows("collapse", row_off, ev, sum, sumsq, len)
+        c = CCollapseCfg(nm, int(trim))
+        if self.res is None and self.handle:
+            r = CResult()                                   # (as events(): a batch that has not been run gets the library's SQG_ESEQUENCE below)
+            ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
+        else:
+            ne = int(self.n_events)
+        dts = dict(ob_rows=torch.int32, ob_len=torch.int64, ob_sum=torch.int64, ob_sumsq=torch.int64, mean=torch.float32, sd=torch.float32, rd_dropped=torch.int32)
+        shapes = {n: (self.n_reads if n == "rd_dropped" else ne, dt) for n, dt in dts.items()}
+        return self._table("sqg_batch_collapse", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CCollapseOut, COLLAPSE_OUTPUTS, shapes, want,
+                           n_rows=nr, row_off=off, n_events=ne)
+
+    def _origin(self, who, origin):
+        """the C origin of pileup() / pileup_rows() (None: the sampler's) and the arrays it points into"""
+        if origin is None:
+            return None, None
+        key0, step = np.ascontiguousarray(origin[0], np.int64), np.ascontiguousarray(origin[1], np.int8)
+        if key0.shape != (self.n_reads,) or step.shape != (self.n_reads,):
+            raise SqgError(-1, who, f"origin=(key0, step) must be two arrays of {self.n_reads} elements")
+        return COrigin(key0.ctypes.data_as(C.POINTER(C.c_int64)), step.ctypes.data_as(C.POINTER(C.c_int8))), (key0, step)
+
+    def pileup_rows(self, p: Pileup, row_off, ev, sum, sumsq, len, origin=None):       # noqa: A002
+        """Adds the OBSERVED events of the rows -- those of collapse(), taken the same way -- to the pileup `p` of
+        SignalGenerator.new_pileup() under the rules of Batch.pileup() (sqg_batch_pileup_rows, include/sqg_collapse.h): one count per event
+        that has a row, its dwell the rows' samples, mean and sd those of collapse() under p's norm and trim.  Returns (counted, outside,
+        unseen, dropped): unseen are the events that would count and have no row, dropped the rows that are assigned to no event of their
+        read.  origin as in pileup()."""
+        import torch
+        _need(self.gen.L, "sqg_batch_pileup_rows", "sqg_collapse.h", "pileup_rows")
+        off, _, cin, keep = self._rows("pileup_rows", row_off, ev, sum, sumsq, len)
+        org, held = self._origin("pileup_rows", origin)
+        out = _ptrs(CPileupOut, (getattr(p, n) for n in PILEUP_OUTPUTS))
+        st = CPileupRowsStat()
+        torch.cuda.synchronize(torch.device("cuda", self.gen.device))     # (the zero fills or the caller's own work on the sums and the rows, before another stream touches them)
+        self._call("sqg_batch_pileup_rows", C.byref(p.cfg), C.byref(org) if org is not None else None, off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin),
+                   C.byref(out), C.byref(st))
+        return int(st.counted), int(st.outside), int(st.unseen), int(st.dropped)
+
     def pileup(self, p: Pileup, origin=None):
         """Adds the batch's events to the pileup `p` of SignalGenerator.new_pileup() (sqg_batch_pileup, include/sqg_pileup.h) and returns
         (counted, outside).  origin=(key0, step): numpy arrays [n_reads] (int64, int8) in place of the sampler's origin -- for staged
         batches, or another coordinate system"""
         import torch
         _need(self.gen.L, "sqg_batch_pileup", "sqg_pileup.h", "pileup")
-        org = None
-        if origin is not None:
-            key0, step = np.ascontiguousarray(origin[0], np.int64), np.ascontiguousarray(origin[1], np.int8)
-            if key0.shape != (self.n_reads,) or step.shape != (self.n_reads,):
-                raise SqgError(-1, "pileup", f"origin=(key0, step) must be two arrays of {self.n_reads} elements")
-            org = COrigin(key0.ctypes.data_as(C.POINTER(C.c_int64)), step.ctypes.data_as(C.POINTER(C.c_int8)))
+        org, held = self._origin("pileup", origin)
         out = _ptrs(CPileupOut, (getattr(p, n) for n in PILEUP_OUTPUTS))
         st = CPileupStat()
         torch.cuda.synchronize(torch.device("cuda", self.gen.device))     # (the zero fills or the caller's own work on the sums, before another stream adds to them)

@@ -136,10 +136,10 @@ struct EventScratch {
     void release() { *this = EventScratch(); }
 };
 
-// device scratch of sqg_batch_pileup (h_pileup.h): the reads' origins, the counters
+// device scratch of sqg_batch_pileup and sqg_batch_pileup_rows (h_pileup.h, h_collapse.h): the reads' origins, the counters
 struct PileupScratch {
     DevBuf<PileRead> d_pr; std::vector<PileRead> h_pr;         // [n_reads] origin and insert of every read, device and host
-    DevBuf<unsigned long long> d_stat;                         // {counted, outside}
+    DevBuf<unsigned long long> d_stat;                         // {counted, outside, unseen, dropped} (sqg_batch_pileup: the first two)
     void release() { *this = PileupScratch(); }
 };
 
@@ -157,6 +157,14 @@ struct AlignScratch {
     DevBuf<ulonglong2> d_mask; DevBuf<int> d_lo;               // [n_rows] the two move-code bits of every band cell, the band's first target
     DevBuf<int> d_end;                                         // [n_reads] the target the best path ends at, -1: none
     void release() { *this = AlignScratch(); }
+};
+
+// device scratch of sqg_batch_collapse and sqg_batch_pileup_rows (h_collapse.h): the row offsets, and the per-event sums the caller did not ask for
+struct CollapseScratch {
+    DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
+    DevBuf<unsigned int> d_rows;                               // [n_events] rows assigned to every event
+    DevBuf<unsigned long long> d_len, d_sum, d_sumsq;          // [n_events] the sums of their len, sum and sumsq
+    void release() { *this = CollapseScratch(); }
 };
 
 struct sqg_ctx {
@@ -299,6 +307,7 @@ struct sqg_ctx {
     PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
     DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
     AlignScratch align;                                        // sqg_batch_align (h_align.h)
+    CollapseScratch collapse;                                  // sqg_batch_collapse, sqg_batch_pileup_rows (h_collapse.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -114,11 +114,11 @@ __device__ __forceinline__ EventAt evtab_event(const EventParams& Q, const long 
 
 // mean / sd of an event of read r from its sums, as include/sqg_events.h states them: one rounding per operation (the build has
 // -ffp-contract=off); double sqrt is correctly rounded on this device, as the exact sample path relies on (k_common.h: box_muller_exact)
+// (evtab_derive_d: on the three as doubles -- evtab_derive for an event's own sums, k_collapse.h for sums over rows, whose length has 64 bits)
 template <bool PA>
-__device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, const int len, const EventAcc& A, float* mean, float* sd) {
-    const double dl = (double)len, ds = (double)A.sum;
+__device__ __forceinline__ void evtab_derive_d(const EventParams& Q, const int r, const double dl, const double ds, const double dq, float* mean, float* sd) {
     const double m = ds / dl;
-    double v = ((double)A.sq - ds * m) / dl;
+    double v = (dq - ds * m) / dl;
     v = v < 0 ? 0 : v;
     const double s = sqrt(v);
     if (PA) {
@@ -130,6 +130,10 @@ __device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, 
         *mean = (float)((m - (double)cs.x) * (double)cs.y);
         *sd = (float)(s * (double)cs.y);
     }
+}
+template <bool PA>
+__device__ __forceinline__ void evtab_derive(const EventParams& Q, const int r, const int len, const EventAcc& A, float* mean, float* sd) {
+    evtab_derive_d<PA>(Q, r, (double)len, (double)A.sum, (double)A.sq, mean, sd);
 }
 
 // The six columns of sums of row i (an event of the table, a row of the detector's) of read r, mean / sd among them: those the caller

@@ -19,10 +19,57 @@ struct PileupParams {
     unsigned int segs;
     long long lo, hi;
     unsigned int* n; long long *dwell, *dwell_sq, *mean_sum, *mean_sq, *sd_sum;   // the caller's [planes][hi - lo], may be null
-    unsigned long long* stat;                                 // {counted, outside}
+    unsigned long long* stat;                                 // {counted, outside}; k_pileup_rows: {counted, outside, unseen}
 };
 
 __device__ __forceinline__ long long pileup_q(const float x) { return (long long)rint((double)x * 4096.0); }
+
+// Whether event i of read r counts before the window is looked at, its key and its plane: include/sqg_pileup.h's rules as k_pileup below
+// states them, as a function for k_pileup_rows (k_collapse.h).  k_pileup keeps its own lines: calling these two functions from it reorders
+// three pairs of its instructions (same 680 / 708 instructions, same registers), and it is to stay instruction-identical.
+struct PileWhere { bool eligible; long long key; int plane; };
+__device__ __forceinline__ PileWhere pileup_where(const EventParams& Q, const PileupParams& U, const long long i, const int r) {
+    long long key = 0;
+    bool eligible = false;
+    int plane = 0;
+    const PileRead pr = U.pr[r];
+    if (U.by_kmer) {
+        eligible = pr.step != 0 && ((U.segs >> U.seg[i]) & 1u);
+        key = (long long)U.kmer[i];
+    } else {
+        const ReadDesc rd = Q.bv.reads[r];
+        const long long e = i - rd.ev_off;
+        const long long j = e - pr.first;
+        eligible = pr.step != 0 && e < rd.ne0 && j >= 0 && j <= (long long)pr.L - U.k;
+        key = pr.key0 + (long long)pr.step * j;
+    }
+    if (U.split_strand) plane = pr.step < 0 ? 1 : 0;
+    if (U.split_meth && eligible) {
+        bool m = false;
+        uint32_t x = U.kmer[i];
+        for (int q = 0; q < U.k; q++) { m |= x % 5u == 3u; x /= 5u; }
+        plane += m ? (U.split_strand ? 2 : 1) : 0;
+    }
+    return {eligible, key, plane};
+}
+
+// The adds of one counted event of `len` samples -- the sum over its rows: 64 bits -- into element `at` of the caller's arrays; derive(&mean,
+// &sd) is called only where a mean is wanted and len > 0.  k_pileup_rows; k_pileup's own adds below are the same lines on an int.
+template <class Derive>
+__device__ __forceinline__ void pileup_add(const PileupParams& U, const long long at, const long long len, const bool want_samples, Derive derive) {
+    if (U.n) __hip_atomic_fetch_add(U.n + at, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (len <= 0) return;                                                     // no sample, no mean: n only
+    if (U.dwell) __hip_atomic_fetch_add(U.dwell + at, len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (U.dwell_sq) __hip_atomic_fetch_add(U.dwell_sq + at, (long long)((unsigned long long)len * (unsigned long long)len), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // modulo 2^64
+    if (want_samples) {
+        float mean, sd;
+        derive(&mean, &sd);
+        const long long qm = pileup_q(mean);
+        if (U.mean_sum) __hip_atomic_fetch_add(U.mean_sum + at, qm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (U.mean_sq) __hip_atomic_fetch_add(U.mean_sq + at, (long long)((unsigned long long)qm * (unsigned long long)qm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (U.sd_sum) __hip_atomic_fetch_add(U.sd_sum + at, pileup_q(sd), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
 
 template <bool PA>
 __global__ __launch_bounds__(CHUNK_WG) void k_pileup(EventParams Q, PileupParams U) {
