@@ -5,7 +5,7 @@
  * stored samples.  The step every such tool takes next -- f5c / nanopolish eventalign, UNCALLED4, the resquiggle in front of m6Anet,
  * xPore and Nanocompore -- assigns each detected row to a k-mer of the read's sequence.  This call makes that assignment on the device
  * with a banded dynamic programme over (row, true event), so that an aligner's row-to-k-mer assignment can be compared with the truth
- * the simulator holds (sqg_detect_out_t.true_ev).  It is NOT f5c's aligner: no scaling is estimated (the simulator's is known), the
+ * the simulator holds (sqg_detect_out_t.true_ev).  It is NOT f5c's aligner: no scaling is estimated (the simulator's is known; sqg_scale.h has the estimate and this call under one), the
  * score is an absolute difference of levels, not a log-probability, and every number is an exact integer.
  *
  * The rule below is the contract: exact integers throughout, no floating point.

@@ -90,7 +90,7 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
-             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS")
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS", "SQG_TEST_SCALE_GRID")
 
 # include/sqg_chunks.h: bound by load_library only when the library has them (the CPU backend does not)
 EXPORTS_CHUNKS = ("sqg_chunk_plan", "sqg_batch_chunks")
@@ -207,6 +207,29 @@ class CAlignOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ALIGN_OUTPUTS]
 
 
+# include/sqg_scale.h: bound the same way
+EXPORTS_SCALE = ("sqg_batch_scale", "sqg_batch_align_scaled")
+SCALE_MOMENTS, SCALE_FIT = 0, 1
+SCALE_INPUTS = ("sum", "len", "ev")
+SCALE_OUTPUTS = ("n", "nx", "sy", "syy", "sx", "sxx", "sxy", "gain", "shift", "rd_dropped")
+
+
+class CScaleCfg(C.Structure):
+    _fields_ = [("mode", C.c_uint32)]
+
+
+class CScaleIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SCALE_INPUTS]
+
+
+class CScaleOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SCALE_OUTPUTS]
+
+
+class CAlignScale(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("gain", "shift")]
+
+
 # include/sqg_collapse.h: bound the same way
 EXPORTS_COLLAPSE = ("sqg_batch_collapse", "sqg_batch_pileup_rows")
 COLLAPSE_INPUTS = ("ev", "sum", "sumsq", "len")
@@ -256,12 +279,14 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
     (EXPORTS_DETECT, {"sqg_detect_plan": (CDetectCfg,) + _PLAN, "sqg_batch_detect": (CDetectCfg, CDetectOut)}),
     (EXPORTS_ALIGN, {"sqg_batch_align": (CAlignCfg, C.c_int64, CAlignIn, CAlignOut)}),
+    (EXPORTS_SCALE, {"sqg_batch_scale": (CScaleCfg, C.c_int64, CScaleIn, CScaleOut),
+                     "sqg_batch_align_scaled": (CAlignCfg, C.c_int64, CAlignIn, CAlignScale, CAlignOut)}),
     (EXPORTS_COLLAPSE, {"sqg_batch_collapse": (CCollapseCfg, C.c_int64, CCollapseIn, CCollapseOut),
                         "sqg_batch_pileup_rows": (CPileupCfg, COrigin, C.c_int64, CCollapseIn, CPileupOut, CPileupRowsStat)}),
 )
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
-          "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}}
+          "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}, "mode": {"moments": SCALE_MOMENTS, "fit": SCALE_FIT}}
 
 
 def _enum(who, **given):
@@ -818,16 +843,19 @@ class Batch:
         shapes = {n: (self.n_reads if n in ("med2", "mad4") else nr, dt) for n, dt in dts.items()}
         return self._table("sqg_batch_detect", (C.byref(c),), CDetectOut, DETECT_OUTPUTS, shapes, want, n_rows=nr, det_off=off)
 
-    def align(self, row_off, sum, len, cfg=None, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
+    def align(self, row_off, sum, len, cfg=None, outputs=None, scale=None) -> Chunks:       # noqa: A002  (the header's names)
         """The rows [row_off[r], row_off[r+1]) of sum / len -- Batch.detect()'s det_off, sum and dt_len, or any other segmentation of the
         reads -- aligned to the true events of read r by a banded dynamic programme in exact integers, on the device (sqg_batch_align,
         include/sqg_align.h).  row_off: [n_reads+1] integers on the host; sum (int64) and len (int32): torch tensors of row_off[-1]
         elements on the context's device.  cfg: (stay_pen, skip_pen, cost_cap), default SQG_ALIGN_DEFAULT.  torch tensors al_ev
         [n_rows] (int64: the row of Batch.events() a row is aligned to, -1: none), al_cost [n_reads] (int64: the cost of the read's best
         path, -1: none), al_edge [n_reads] (int32: rows on the moving band's rim).  outputs: the names wanted (default all); the others
-        are None."""
+        are None.  scale=(gain, shift): int32 tensors [n_reads] on the context's device, a row's level taken as (gain * q >> 16) + shift
+        (gain in Q16, shift in 1/256 code: Batch.scale()'s estimate, sqg_batch_align_scaled, include/sqg_scale.h); None: the rows as they stand."""
         import torch
         _need(self.gen.L, "sqg_batch_align", "sqg_align.h", "align")
+        if scale is not None:
+            _need(self.gen.L, "sqg_batch_align_scaled", "sqg_scale.h", "align")
         three = ALIGN_DEFAULT if cfg is None else cfg
         if isinstance(three, str) or _len(three) != 3:
             raise SqgError(-1, "align", f"cfg must be (stay_pen, skip_pen, cost_cap), not {cfg!r}")
@@ -844,7 +872,45 @@ class Batch:
         keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
         cin = CAlignIn(sum.data_ptr() if sum.numel() else keep.data_ptr(), len.data_ptr() if len.numel() else keep.data_ptr())
         shapes = dict(al_ev=(nr, torch.int64), al_cost=(self.n_reads, torch.int64), al_edge=(self.n_reads, torch.int32))
-        return self._table("sqg_batch_align", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CAlignOut, ALIGN_OUTPUTS, shapes, want,
+        args = (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin))
+        if scale is None:
+            return self._table("sqg_batch_align", args, CAlignOut, ALIGN_OUTPUTS, shapes, want, n_rows=nr, row_off=off)
+        if isinstance(scale, torch.Tensor) or _len(scale) != 2:
+            raise SqgError(-1, "align", "scale must be (gain, shift)")
+        for name, t in zip(("gain", "shift"), scale):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous() and t.numel() == self.n_reads):
+                raise SqgError(-1, "align", f"scale: {name} must be a contiguous {torch.int32} tensor of {self.n_reads} elements on {dev}")
+        csc = CAlignScale(*(t.data_ptr() if t.numel() else keep.data_ptr() for t in scale))
+        return self._table("sqg_batch_align_scaled", args + (C.byref(csc),), CAlignOut, ALIGN_OUTPUTS, shapes, want, n_rows=nr, row_off=off)
+
+    def scale(self, row_off, sum, len, ev=None, mode=None, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
+        """The per-read shift and scale a tool would estimate from the rows [row_off[r], row_off[r+1]) of sum / len, on the device
+        (sqg_batch_scale, include/sqg_scale.h).  mode "moments" (the default without ev): the rows' mean and variance against those of ALL
+        the read's true events.  mode "fit" (the default with ev): least squares of the event's level on the row's over the rows that ev
+        -- Batch.align()'s al_ev, the detector's true_ev, or the caller's own -- assigns to an event of their own read; the others are
+        dropped.  row_off: [n_reads+1] integers on the host; sum, ev (int64) and len (int32): torch tensors of row_off[-1] elements on the
+        context's device.  torch tensors [n_reads]: n, nx, sy, syy, sx, sxx, sxy (int64: the exact sums in 1/16 code), gain (int32, Q16),
+        shift (int32, 1/256 code) -- what Batch.align(scale=(gain, shift)) takes; the truth of a simulated read is (65536, 0) --,
+        rd_dropped (int32).  outputs: the names wanted (default all); the others are None."""
+        import torch
+        _need(self.gen.L, "sqg_batch_scale", "sqg_scale.h", "scale")
+        md, = _enum("scale", mode=("moments" if ev is None else "fit") if mode is None else mode)
+        want = _want(outputs, SCALE_OUTPUTS, "scale")
+        off = np.ascontiguousarray(row_off, np.int64)
+        if off.shape != (self.n_reads + 1,):
+            raise SqgError(-1, "scale", f"row_off must have {self.n_reads + 1} elements")
+        nr = max(int(off[-1]), 0)
+        dev = torch.device("cuda", self.gen.device)
+        for name, t, dt in (("sum", sum, torch.int64), ("len", len, torch.int32), ("ev", ev, torch.int64)):
+            if t is None and name == "ev":
+                continue                                        # (the library says which mode needs it)
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
+                raise SqgError(-1, "scale", f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
+        keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
+        cin = CScaleIn(*(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in (sum, len, ev)))
+        c = CScaleCfg(md)
+        shapes = {n: (self.n_reads, torch.int32 if n in ("gain", "shift", "rd_dropped") else torch.int64) for n in SCALE_OUTPUTS}
+        return self._table("sqg_batch_scale", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CScaleOut, SCALE_OUTPUTS, shapes, want,
                            n_rows=nr, row_off=off)
 
     def _rows(self, who, row_off, ev, sum, sumsq, len):       # noqa: A002

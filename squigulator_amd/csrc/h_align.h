@@ -1,16 +1,18 @@
 // h_align.h -- sqg_batch_align: banded alignment of the caller's event rows to the true events of their reads, left on the device
 // Host side of include/sqg_align.h; included by sqg_hip.hip behind h_detect.h.  The opening of the checks, the batch's view and the
-// lifetime rule are h_chunks.h's, the scan pass and its parameters h_events_table.h's.
+// lifetime rule are h_chunks.h's, the scan pass and its parameters h_events_table.h's.  The body is stated once (align_run):
+// sqg_batch_align runs it without a scaling, sqg_batch_align_scaled (h_scale.h, include/sqg_scale.h) with the caller's.
 #pragma once
 
-extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, const int64_t* row_off,
-                               const sqg_align_in_t* in, const sqg_align_out_t* out) {
-    static const char who[] = "sqg_batch_align";
+// `scaled`: the call takes a scaling, *scale (checked behind out); else scale is null and the rows are taken as they stand
+static int align_run(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, const int64_t* row_off, const sqg_align_in_t* in,
+                     const bool scaled, const sqg_align_scale_t* scale, const sqg_align_out_t* out, const char* who) {
     int rc = check_open(c, b, cfg, "cfg", who);
     if (rc) return rc;
     const Check K{c, who};
     if ((rc = K.null(row_off, "row_off")) || (rc = K.null(in, "in")) || (rc = K.null(in->sum, "in->sum")) || (rc = K.null(in->len, "in->len")) ||
         (rc = K.null(out, "out"))) return rc;
+    if (scaled && ((rc = K.null(scale, "scale")) || (rc = K.null(scale->gain, "scale->gain")) || (rc = K.null(scale->shift, "scale->shift")))) return rc;
     if (cfg->stay_pen < 0 || cfg->stay_pen > (1 << 24)) return K.bad("stay_pen must be in 0 .. 1<<24");
     if (cfg->skip_pen < 0 || cfg->skip_pen > (1 << 24)) return K.bad("skip_pen must be in 0 .. 1<<24");
     if (cfg->cost_cap < 1 || cfg->cost_cap > (1 << 24)) return K.bad("cost_cap must be in 1 .. 1<<24");
@@ -36,13 +38,14 @@ extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg
     P.stay_pen = cfg->stay_pen; P.skip_pen = cfg->skip_pen; P.cost_cap = cfg->cost_cap;
     P.tr_mask = X.d_mask.p; P.tr_lo = X.d_lo.p; P.end_j = X.d_end.p;
     P.al_ev = (long long*)out->al_ev; P.al_cost = (long long*)out->al_cost; P.al_edge = out->al_edge;
+    P.gain = scaled ? scale->gain : nullptr; P.shift = scaled ? scale->shift : nullptr;
     // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone; none for a batch without events, whose reads have no target)
     EventParams Q{P.bv, (const float2*)nullptr, b->n_events};
     if (b->n_events > 0 && (rc = evtab_scan_run(c, Q, EVC_LEVEL))) return rc;
     P.level_raw = Q.level_raw;
     // the forward pass: every read's band row by row, its end, and the trace when a path is wanted
-    if (want_trace) hipLaunchKernelGGL(k_align_forward<true>, dim3((unsigned)n), dim3(64), 0, st, P);
-    else hipLaunchKernelGGL(k_align_forward<false>, dim3((unsigned)n), dim3(64), 0, st, P);
+    const auto forward = [&](auto TR, auto SC) { hipLaunchKernelGGL((k_align_forward<decltype(TR)::value, decltype(SC)::value>), dim3((unsigned)n), dim3(64), 0, st, P); };
+    dispatch(want_trace, scaled, forward);
     if ((rc = launched(c, "k_align_forward"))) return rc;
     // the traceback
     if (want_trace) {
@@ -51,4 +54,9 @@ extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg
     }
     HIPCHK(c, hipStreamSynchronize(st));
     return SQG_OK;
+}
+
+extern "C" int sqg_batch_align(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, const int64_t* row_off,
+                               const sqg_align_in_t* in, const sqg_align_out_t* out) {
+    return align_run(c, b, cfg, row_off, in, false, nullptr, out, "sqg_batch_align");
 }

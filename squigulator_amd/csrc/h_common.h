@@ -167,6 +167,13 @@ struct CollapseScratch {
     void release() { *this = CollapseScratch(); }
 };
 
+// device scratch of sqg_batch_scale (h_scale.h): the row offsets and the per-read sums
+struct ScaleScratch {
+    DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
+    DevBuf<unsigned long long> d_acc;                          // [SCL_COLS][n_reads] k_scale_sums' columns
+    void release() { *this = ScaleScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -308,6 +315,7 @@ struct sqg_ctx {
     DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
     AlignScratch align;                                        // sqg_batch_align (h_align.h)
     CollapseScratch collapse;                                  // sqg_batch_collapse, sqg_batch_pileup_rows (h_collapse.h)
+    ScaleScratch scale;                                        // sqg_batch_scale (h_scale.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -1,7 +1,7 @@
 // k_align.h -- banded alignment of event rows to the true events of their read (include/sqg_align.h): the forward pass, then the traceback
 // Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_detect.h.
 //
-//   k_align_forward<TRACE>  a row of the dynamic programme has no dependency inside itself, so one wavefront holds one read's band, one cell per
+//   k_align_forward<TRACE, SCALED>  a row of the dynamic programme has no dependency inside itself, so one wavefront holds one read's band, one cell per
 //                        lane, one wavefront per workgroup (the hardware hands the reads out: they differ in length).  D of the row before lives
 //                        in registers; a row takes its three predecessors from them by lane shift, offset by how far the band moved (0..2).
 //                        The band's move is one wavefront argmin per row: a 64-bit minimum as two 32-bit ones (four DPP steps inside the rows
@@ -10,7 +10,9 @@
 //                        rows at a time (one row per lane, read back by lane index); Lv 64 targets at a time into two registers that
 //                        cover [tb, tb + 128), from which the band's levels are re-read by lane shift on the rows at which the band moves.
 //                        TRACE: the move codes of a row are two ballots, one per code bit; lane 0 stores them (16 B) and lo_i (4 B).
-//                        No LDS, no floating point.
+//                        No LDS, no floating point.  SCALED (sqg_batch_align_scaled, include/sqg_scale.h): the read's gain and shift, two
+//                        wavefront-uniform values clamped into their ranges, are applied where the tile's q is made -- a multiply, a shift
+//                        and an add per 64 rows and lane -- and nothing in the per-row loop changes.
 //   k_align_trace        one wavefront per read again.  The traceback is a dependent chain along the read, but only in j: the trace rows'
 //                        addresses do not depend on it.  So the wavefront loads 64 trace rows at once, one per lane, walks them back with
 //                        lane reads -- wavefront-uniform, scalar arithmetic --, each lane keeps the j of its own row, and al_ev goes out as
@@ -28,6 +30,7 @@ struct AlignParams {
     ulonglong2* tr_mask; int* tr_lo;                 // [n_rows] the trace: the two code bits of the band's cells, lo_i (scratch)
     int* end_j;                                      // [n_reads] e, -1: none (scratch)
     long long* al_ev; long long* al_cost; int* al_edge;   // the caller's, may be null
+    const int* gain; const int* shift;               // [n_reads] the caller's scaling (k_align_forward<., true> alone; null otherwise)
 };
 
 // the smallest of v over the wavefront, in every lane (all 64 lanes active): quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
@@ -56,7 +59,7 @@ __device__ __forceinline__ unsigned long long aln_prev(const unsigned long long 
     return (unsigned)src < 64u ? v : ALN_INF;
 }
 
-template <bool TRACE>
+template <bool TRACE, bool SCALED>
 __global__ __launch_bounds__(64) void k_align_forward(AlignParams P) {
     const BatchView& V = P.bv;
     const int r = blockIdx.x, lane = threadIdx.x;
@@ -73,6 +76,8 @@ __global__ __launch_bounds__(64) void k_align_forward(AlignParams P) {
     auto level = [&](const long long j) { return j < T ? 256 * (int)lvp[rna ? T - 1 - j : j] : 0; };      // Lv[j]; past the read 0, never used
     const unsigned long long stay = (unsigned long long)P.stay_pen, skip = (unsigned long long)P.skip_pen;
     const int cap = P.cost_cap;
+    const long long gain = SCALED ? min(max(P.gain[r], 1), 1 << 20) : 65536;                 // (out of range: clamped, as the header says)
+    const long long off = SCALED ? min(max(P.shift[r], -(1 << 26)), 1 << 26) : 0;
     long long tb = 0;                                             // L0 holds Lv[tb + lane], L1 Lv[tb + 64 + lane]
     int L0 = level(lane), L1 = level(64 + lane);
     int lo = 0, lv = L0, shift = 0;                               // the band's first target, its levels, how far it moved before this row
@@ -87,7 +92,9 @@ __global__ __launch_bounds__(64) void k_align_forward(AlignParams P) {
             const long long p = (long long)((unsigned long long)s << 8);
             long long q = p / n;
             if (p % n != 0 && p < 0) q--;                         // floor
-            qt = (int)min(max(q, -(1LL << 26)), 1LL << 26);
+            q = min(max(q, -(1LL << 26)), 1LL << 26);
+            if (SCALED) q = min(max(((gain * q) >> 16) + off, -(1LL << 26)), 1LL << 26);      // (|gain q| <= 2^46; >> of a negative: arithmetic, a floor)
+            qt = (int)q;
         }
         for (int t = 0; t < cnt; t++) {
             const int i = (int)i0 + t;
