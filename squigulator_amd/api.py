@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h and include/sqg_collapse.h (squigulator_amd/csrc/libsqg_hip.so).
+"""ctypes binding of the C ABI in include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h, include/sqg_collapse.h and include/sqg_scale.h (squigulator_amd/csrc/libsqg_hip.so).
 
 This is plumbing for tests and bench.py; the product is the shared library.  There is NO CPU
 fallback: if the HIP library is missing or no GPU is usable, construction raises.
@@ -803,11 +803,7 @@ class Batch:
         nm, = _enum("events", norm=norm)
         want = _want(outputs, EVENT_OUTPUTS, "events")
         cfg = CEventCfg(nm, int(trim))
-        if self.res is None and self.handle:
-            r = CResult()                                   # (the row count; a batch that has not been run: the library's SQG_ESEQUENCE below)
-            ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
-        else:
-            ne = int(self.n_events)
+        ne = self._n_events()
         dts = dict(ev_read=torch.int32, ev_start=torch.int64, ev_len=torch.int32, sum=torch.int64, sumsq=torch.int64, vmin=torch.int16, vmax=torch.int16,
                    kmer=torch.int32, level_raw=torch.int16, seg=torch.uint8, mean=torch.float32, sd=torch.float32, med2=torch.int32, mad4=torch.int32)
         shapes = {n: (self.n_reads if n in ("med2", "mad4") else ne, dt) for n, dt in dts.items()}
@@ -861,16 +857,8 @@ class Batch:
             raise SqgError(-1, "align", f"cfg must be (stay_pen, skip_pen, cost_cap), not {cfg!r}")
         c = CAlignCfg(*(int(v) for v in three))
         want = _want(outputs, ALIGN_OUTPUTS, "align")
-        off = np.ascontiguousarray(row_off, np.int64)
-        if off.shape != (self.n_reads + 1,):
-            raise SqgError(-1, "align", f"row_off must have {self.n_reads + 1} elements")
-        nr = max(int(off[-1]), 0)
+        off, nr, cin, keep = self._rows("align", row_off, CAlignIn, (sum, len))
         dev = torch.device("cuda", self.gen.device)
-        for name, t, dt in (("sum", sum, torch.int64), ("len", len, torch.int32)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
-                raise SqgError(-1, "align", f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
-        keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
-        cin = CAlignIn(sum.data_ptr() if sum.numel() else keep.data_ptr(), len.data_ptr() if len.numel() else keep.data_ptr())
         shapes = dict(al_ev=(nr, torch.int64), al_cost=(self.n_reads, torch.int64), al_edge=(self.n_reads, torch.int32))
         args = (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin))
         if scale is None:
@@ -896,40 +884,37 @@ class Batch:
         _need(self.gen.L, "sqg_batch_scale", "sqg_scale.h", "scale")
         md, = _enum("scale", mode=("moments" if ev is None else "fit") if mode is None else mode)
         want = _want(outputs, SCALE_OUTPUTS, "scale")
-        off = np.ascontiguousarray(row_off, np.int64)
-        if off.shape != (self.n_reads + 1,):
-            raise SqgError(-1, "scale", f"row_off must have {self.n_reads + 1} elements")
-        nr = max(int(off[-1]), 0)
-        dev = torch.device("cuda", self.gen.device)
-        for name, t, dt in (("sum", sum, torch.int64), ("len", len, torch.int32), ("ev", ev, torch.int64)):
-            if t is None and name == "ev":
-                continue                                        # (the library says which mode needs it)
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
-                raise SqgError(-1, "scale", f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
-        keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
-        cin = CScaleIn(*(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in (sum, len, ev)))
+        off, nr, cin, keep = self._rows("scale", row_off, CScaleIn, (sum, len, ev), ("ev",))
         c = CScaleCfg(md)
         shapes = {n: (self.n_reads, torch.int32 if n in ("gain", "shift", "rd_dropped") else torch.int64) for n in SCALE_OUTPUTS}
         return self._table("sqg_batch_scale", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CScaleOut, SCALE_OUTPUTS, shapes, want,
                            n_rows=nr, row_off=off)
 
-    def _rows(self, who, row_off, ev, sum, sumsq, len):       # noqa: A002
-        """the rows of collapse() / pileup_rows(), checked as align() checks its own: (row_off as int64, n_rows, the C struct of addresses,
-        what keeps them alive)"""
+    def _rows(self, who, row_off, struct, cols, optional=()):
+        """the caller's rows of align() / scale() / collapse() / pileup_rows(): row_off, and cols, a tensor for every field of the call's C
+        `struct` in its order (int64, `len` int32); one named in `optional` may be None (the library says what needs it).  Returns (row_off
+        as int64, n_rows, the struct of the columns' addresses, what keeps them valid until the library call has returned)"""
         import torch
         off = np.ascontiguousarray(row_off, np.int64)
         if off.shape != (self.n_reads + 1,):
             raise SqgError(-1, who, f"row_off must have {self.n_reads + 1} elements")
         nr = max(int(off[-1]), 0)
         dev = torch.device("cuda", self.gen.device)
-        for name, t, dt in (("ev", ev, torch.int64), ("sum", sum, torch.int64), ("sumsq", sumsq, torch.int64), ("len", len, torch.int32)):
-            if t is None and name == "sumsq":
-                continue                                        # (the library says which outputs need it)
+        for (name, _), t in zip(struct._fields_, cols):
+            dt = torch.int32 if name == "len" else torch.int64
+            if t is None and name in optional:
+                continue
             if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() >= nr):
                 raise SqgError(-1, who, f"{name} must be a contiguous {dt} tensor of at least {nr} elements on {dev}")
         keep = torch.zeros(1, dtype=torch.int64, device=dev)  # (a valid address for an empty table: NULL is an error, and nothing is read)
-        cin = CCollapseIn(*(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in (ev, sum, sumsq, len)))
-        return off, nr, cin, keep
+        return off, nr, struct(*(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in cols)), keep
+
+    def _n_events(self):
+        """a table's row count; a batch not yet waited for is waited for here (one not run: 0, and the library's SQG_ESEQUENCE behind)"""
+        if self.res is None and self.handle:
+            r = CResult()
+            return int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
+        return int(self.n_events)
 
     def collapse(self, row_off, ev, sum, sumsq, len, norm="pa", trim: bool = False, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
         """The observed event table: the rows [row_off[r], row_off[r+1]) of sum / sumsq / len -- Batch.detect()'s det_off, sum, sumsq and
@@ -944,13 +929,9 @@ class Batch:
         _need(self.gen.L, "sqg_batch_collapse", "sqg_collapse.h", "collapse")
         nm, = _enum("collapse", norm=norm)
         want = _want(outputs, COLLAPSE_OUTPUTS, "collapse")
-        off, nr, cin, keep = self._rows("collapse", row_off, ev, sum, sumsq, len)
+        off, nr, cin, keep = self._rows("collapse", row_off, CCollapseIn, (ev, sum, sumsq, len), ("sumsq",))
         c = CCollapseCfg(nm, int(trim))
-        if self.res is None and self.handle:
-            r = CResult()                                   # (as events(): a batch that has not been run gets the library's SQG_ESEQUENCE below)
-            ne = int(r.n_events) if self.gen.L.sqg_batch_wait(self.gen.ctx, self.handle, C.byref(r)) == 0 else 0
-        else:
-            ne = int(self.n_events)
+        ne = self._n_events()
         dts = dict(ob_rows=torch.int32, ob_len=torch.int64, ob_sum=torch.int64, ob_sumsq=torch.int64, mean=torch.float32, sd=torch.float32, rd_dropped=torch.int32)
         shapes = {n: (self.n_reads if n == "rd_dropped" else ne, dt) for n, dt in dts.items()}
         return self._table("sqg_batch_collapse", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CCollapseOut, COLLAPSE_OUTPUTS, shapes, want,
@@ -973,7 +954,7 @@ class Batch:
         read.  origin as in pileup()."""
         import torch
         _need(self.gen.L, "sqg_batch_pileup_rows", "sqg_collapse.h", "pileup_rows")
-        off, _, cin, keep = self._rows("pileup_rows", row_off, ev, sum, sumsq, len)
+        off, _, cin, keep = self._rows("pileup_rows", row_off, CCollapseIn, (ev, sum, sumsq, len), ("sumsq",))
         org, held = self._origin("pileup_rows", origin)
         out = _ptrs(CPileupOut, (getattr(p, n) for n in PILEUP_OUTPUTS))
         st = CPileupRowsStat()

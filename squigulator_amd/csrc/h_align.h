@@ -1,8 +1,28 @@
 // h_align.h -- sqg_batch_align: banded alignment of the caller's event rows to the true events of their reads, left on the device
-// Host side of include/sqg_align.h; included by sqg_hip.hip behind h_detect.h.  The opening of the checks, the batch's view and the
-// lifetime rule are h_chunks.h's, the scan pass and its parameters h_events_table.h's.  The body is stated once (align_run):
-// sqg_batch_align runs it without a scaling, sqg_batch_align_scaled (h_scale.h, include/sqg_scale.h) with the caller's.
+// Host side of include/sqg_align.h; included by sqg_hip.hip behind h_detect.h.  The opening of the checks, the batch's view and the lifetime rule
+// are h_chunks.h's, the scan pass and the targets h_events_table.h's.  Stated once here: the body (align_run: sqg_batch_align runs it without a
+// scaling, sqg_batch_align_scaled of h_scale.h with the caller's) and, for h_collapse.h and h_scale.h too, the caller's rows (rows_off_check, rows_upload).
 #pragma once
+
+// row_off[n+1] of the caller, not NULL: the first row of every read, the rows' number behind them
+static int rows_off_check(const Check& K, int n, const int64_t* row_off) {
+    if (row_off[0] != 0) return K.bad("row_off must start at 0");
+    for (int i = 0; i < n; i++) {
+        if (row_off[i + 1] < row_off[i]) return K.bad("row_off must not decrease");
+        if (row_off[i + 1] - row_off[i] > 0x7fffffffLL) return K.bad("row_off: a read has 2^31 rows or more");
+    }
+    return SQG_OK;
+}
+
+// the checked row_off to the context's scratch, on its stream; *R: the rows as the call's kernels take them
+static int rows_upload(sqg_ctx* c, const BatchView& bv, const int64_t* row_off, RowsIn* R) {
+    const size_t n = (size_t)bv.n_reads;
+    const int rc = c->rows.d_off.need(c, n + 1);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->rows.d_off.p, row_off, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    *R = RowsIn{bv.reads, c->rows.d_off.p, bv.n_reads, (long long)row_off[n]};
+    return SQG_OK;
+}
 
 // `scaled`: the call takes a scaling, *scale (checked behind out); else scale is null and the rows are taken as they stand
 static int align_run(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, const int64_t* row_off, const sqg_align_in_t* in,
@@ -17,32 +37,23 @@ static int align_run(sqg_ctx_t* c, sqg_batch_t* b, const sqg_align_cfg_t* cfg, c
     if (cfg->skip_pen < 0 || cfg->skip_pen > (1 << 24)) return K.bad("skip_pen must be in 0 .. 1<<24");
     if (cfg->cost_cap < 1 || cfg->cost_cap > (1 << 24)) return K.bad("cost_cap must be in 1 .. 1<<24");
     const int n = b->n;
-    if (row_off[0] != 0) return K.bad("row_off must start at 0");
-    for (int i = 0; i < n; i++) {
-        if (row_off[i + 1] < row_off[i]) return K.bad("row_off must not decrease");
-        if (row_off[i + 1] - row_off[i] > 0x7fffffffLL) return K.bad("row_off: a read has 2^31 rows or more");
-    }
-    if ((rc = K.ran(b))) return rc;
+    if ((rc = rows_off_check(K, n, row_off)) || (rc = K.ran(b))) return rc;
     if ((rc = chunk_owned(c, b, who, c->use_dwell_stream)) || n == 0) return rc;
     const bool want_trace = out->al_ev || out->al_edge;
     if (!want_trace && !out->al_cost) return SQG_OK;
     AlignScratch& X = c->align;
-    const long long n_rows = (long long)row_off[n];
-    if ((rc = X.d_off.need(c, (size_t)n + 1)) || (rc = X.d_end.need(c, (size_t)n))) return rc;
-    if (want_trace && ((rc = X.d_mask.need(c, (size_t)std::max<long long>(n_rows, 1))) || (rc = X.d_lo.need(c, (size_t)std::max<long long>(n_rows, 1))))) return rc;
-    const hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(X.d_off.p, row_off, ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    AlignParams P{};
+    AlignParams P{}; RowsIn R{};
     P.bv = batch_view(c, b);
-    P.row_off = X.d_off.p; P.sum = (const long long*)in->sum; P.len = in->len;
+    if ((rc = rows_upload(c, P.bv, row_off, &R)) || (rc = X.d_end.need(c, (size_t)n))) return rc;
+    const size_t n_trace = (size_t)std::max<long long>(R.n_rows, 1);
+    if (want_trace && ((rc = X.d_mask.need(c, n_trace)) || (rc = X.d_lo.need(c, n_trace)))) return rc;
+    const hipStream_t st = c->stream;
+    P.row_off = R.row_off; P.sum = (const long long*)in->sum; P.len = in->len;
     P.stay_pen = cfg->stay_pen; P.skip_pen = cfg->skip_pen; P.cost_cap = cfg->cost_cap;
     P.tr_mask = X.d_mask.p; P.tr_lo = X.d_lo.p; P.end_j = X.d_end.p;
     P.al_ev = (long long*)out->al_ev; P.al_cost = (long long*)out->al_cost; P.al_edge = out->al_edge;
     P.gain = scaled ? scale->gain : nullptr; P.shift = scaled ? scale->shift : nullptr;
-    // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone; none for a batch without events, whose reads have no target)
-    EventParams Q{P.bv, (const float2*)nullptr, b->n_events};
-    if (b->n_events > 0 && (rc = evtab_scan_run(c, Q, EVC_LEVEL))) return rc;
-    P.level_raw = Q.level_raw;
+    if ((rc = evtab_targets(c, P.bv, b->n_events, &P.level_raw))) return rc;      // the targets: every true event's level_raw
     // the forward pass: every read's band row by row, its end, and the trace when a path is wanted
     const auto forward = [&](auto TR, auto SC) { hipLaunchKernelGGL((k_align_forward<decltype(TR)::value, decltype(SC)::value>), dim3((unsigned)n), dim3(64), 0, st, P); };
     dispatch(want_trace, scaled, forward);

@@ -5,17 +5,12 @@
 // (collapse_check) and the row pass with its scratch (collapse_rows_run).
 #pragma once
 
-// the rows' arguments, behind check_open: the NULL checks in the header's order, then row_off as sqg_batch_align checks it
+// the rows' arguments, behind check_open: the NULL checks in the header's order, then row_off (h_align.h: rows_off_check)
 static int collapse_check(const Check& K, const sqg_batch* b, const int64_t* row_off, const sqg_collapse_in_t* in, const void* out) {
     int rc;
     if ((rc = K.null(row_off, "row_off")) || (rc = K.null(in, "in")) || (rc = K.null(in->ev, "in->ev")) || (rc = K.null(in->sum, "in->sum")) ||
         (rc = K.null(in->len, "in->len")) || (rc = K.null(out, "out"))) return rc;
-    if (row_off[0] != 0) return K.bad("row_off must start at 0");
-    for (int i = 0; i < b->n; i++) {
-        if (row_off[i + 1] < row_off[i]) return K.bad("row_off must not decrease");
-        if (row_off[i + 1] - row_off[i] > 0x7fffffffLL) return K.bad("row_off: a read has 2^31 rows or more");
-    }
-    return SQG_OK;
+    return rows_off_check(K, b->n, row_off);
 }
 
 // The row pass on st: the upload of row_off, the sums named in `need` (bit 0 rows, 1 len, 2 sum, 3 sumsq) into the caller's arrays of *own
@@ -26,10 +21,8 @@ static int collapse_rows_run(sqg_ctx* c, sqg_batch* b, const BatchView& bv, cons
     CollapseScratch& X = c->collapse;
     const int n = b->n;
     const size_t ne = (size_t)b->n_events;
-    int rc;
-    if ((rc = X.d_off.need(c, (size_t)n + 1))) return rc;
+    int rc = SQG_OK;
     CollapseParams P{};
-    P.reads = bv.reads; P.row_off = X.d_off.p; P.n_reads = n; P.n_rows = (long long)row_off[n];
     P.ev = (const long long*)in->ev; P.sum = (const long long*)in->sum; P.sumsq = (const long long*)in->sumsq; P.len = in->len;
     P.ob_rows = own ? own->ob_rows : nullptr; P.ob_len = own ? (unsigned long long*)own->ob_len : nullptr;
     P.ob_sum = own ? (unsigned long long*)own->ob_sum : nullptr; P.ob_sumsq = own ? (unsigned long long*)own->ob_sumsq : nullptr;
@@ -44,15 +37,15 @@ static int collapse_rows_run(sqg_ctx* c, sqg_batch* b, const BatchView& bv, cons
     for (int q = 0; q < 4; q++)                                                                      // no kernel is handed a null column it will read
         if (ne && (need >> q & 1u) && !cols[q]) { c->err = "k_collapse_rows: a sum a later pass reads has no memory"; return SQG_EDEVICE; }
     if (P.ob_sumsq && !P.sumsq) { c->err = "k_collapse_rows: ob_sumsq without in->sumsq"; return SQG_EDEVICE; }      // (the callers have refused it)
-    HIPCHK(c, hipMemcpyAsync(X.d_off.p, row_off, ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    if ((rc = rows_upload(c, bv, row_off, &P.rows))) return rc;
     if (P.ob_rows) HIPCHK(c, hipMemsetAsync(P.ob_rows, 0, ne * sizeof(unsigned int), st));
     if (P.ob_len) HIPCHK(c, hipMemsetAsync(P.ob_len, 0, ne * sizeof(unsigned long long), st));
     if (P.ob_sum) HIPCHK(c, hipMemsetAsync(P.ob_sum, 0, ne * sizeof(unsigned long long), st));
     if (P.ob_sumsq) HIPCHK(c, hipMemsetAsync(P.ob_sumsq, 0, ne * sizeof(unsigned long long), st));
     if (P.rd_dropped) HIPCHK(c, hipMemsetAsync(P.rd_dropped, 0, (size_t)n * sizeof(int), st));
     *S = CollapseSums{P.ob_rows, (const long long*)P.ob_len, (const long long*)P.ob_sum, (const long long*)P.ob_sumsq};
-    if (P.n_rows == 0) return SQG_OK;
-    hipLaunchKernelGGL(k_collapse_rows, dim3(flat_grid(c, P.n_rows)), dim3(CHUNK_WG), 0, st, P);
+    if (P.rows.n_rows == 0) return SQG_OK;
+    hipLaunchKernelGGL(k_collapse_rows, dim3(flat_grid(c, P.rows.n_rows)), dim3(CHUNK_WG), 0, st, P);
     return launched(c, "k_collapse_rows");
 }
 

@@ -151,25 +151,30 @@ struct DetectScratch {
     void release() { *this = DetectScratch(); }
 };
 
-// device scratch of sqg_batch_align (h_align.h): the row offsets, the trace of the forward pass and every read's end
-struct AlignScratch {
+// device scratch of the calls that take the caller's rows (h_align.h: rows_upload; h_collapse.h, h_scale.h): the row offsets.  One array serves
+// them all, unlike a ReadPlan, which a later call must find unchanged: every call uploads its own offsets, only that call's kernels on the
+// context's stream read them, and the call synchronises the stream before it returns (tests/test_consumer_order.py).
+struct RowsScratch {
     DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
+    void release() { *this = RowsScratch(); }
+};
+
+// device scratch of sqg_batch_align (h_align.h): the trace of the forward pass and every read's end
+struct AlignScratch {
     DevBuf<ulonglong2> d_mask; DevBuf<int> d_lo;               // [n_rows] the two move-code bits of every band cell, the band's first target
     DevBuf<int> d_end;                                         // [n_reads] the target the best path ends at, -1: none
     void release() { *this = AlignScratch(); }
 };
 
-// device scratch of sqg_batch_collapse and sqg_batch_pileup_rows (h_collapse.h): the row offsets, and the per-event sums the caller did not ask for
+// device scratch of sqg_batch_collapse and sqg_batch_pileup_rows (h_collapse.h): the per-event sums the caller did not ask for
 struct CollapseScratch {
-    DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
     DevBuf<unsigned int> d_rows;                               // [n_events] rows assigned to every event
     DevBuf<unsigned long long> d_len, d_sum, d_sumsq;          // [n_events] the sums of their len, sum and sumsq
     void release() { *this = CollapseScratch(); }
 };
 
-// device scratch of sqg_batch_scale (h_scale.h): the row offsets and the per-read sums
+// device scratch of sqg_batch_scale (h_scale.h): the per-read sums
 struct ScaleScratch {
-    DevBuf<long long> d_off;                                   // [n_reads+1] first row of every read (the caller's row_off)
     DevBuf<unsigned long long> d_acc;                          // [SCL_COLS][n_reads] k_scale_sums' columns
     void release() { *this = ScaleScratch(); }
 };
@@ -313,6 +318,7 @@ struct sqg_ctx {
     EventScratch event;                                        // k_evtab_scan's columns (h_events_table.h: evtab_scan_run)
     PileupScratch pileup;                                      // sqg_batch_pileup (h_pileup.h)
     DetectScratch detect;                                      // sqg_detect_plan, sqg_batch_detect (h_detect.h)
+    RowsScratch rows;                                          // the caller's row offsets (h_align.h: rows_upload)
     AlignScratch align;                                        // sqg_batch_align (h_align.h)
     CollapseScratch collapse;                                  // sqg_batch_collapse, sqg_batch_pileup_rows (h_collapse.h)
     ScaleScratch scale;                                        // sqg_batch_scale (h_scale.h)

@@ -59,6 +59,7 @@ extern "C" void sqg_destroy(sqg_ctx_t* ctx) {
     ctx->event.release();
     ctx->pileup.release();
     ctx->detect.release();
+    ctx->rows.release();
     ctx->align.release();
     ctx->collapse.release();
     ctx->scale.release();

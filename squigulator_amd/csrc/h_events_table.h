@@ -1,7 +1,7 @@
 // h_events_table.h -- sqg_batch_events: the per-event signal table of a batch, left on the device
 // Host side of include/sqg_events.h; included by sqg_hip.hip behind h_sites.h.  The opening of the checks, the batch's view, the lifetime rule and the statistics job are h_chunks.h's.
-// What the calls with a row pass over events share is stated here once: the scan pass (evtab_scan_run), the flat grid's size (flat_grid)
-// and the six columns of sums among a call's outputs (evtab_outputs).  h_pileup.h, h_detect.h and h_align.h use them.
+// What the calls with a row pass over events share is stated here once: the scan pass (evtab_scan_run, evtab_targets), the flat grid's size
+// (flat_grid) and the six columns of sums among a call's outputs (evtab_outputs).  h_pileup.h, h_detect.h, h_align.h, h_collapse.h, h_scale.h.
 #pragma once
 
 enum : unsigned { EVC_START = 1, EVC_READ = 2, EVC_KMER = 4, EVC_SEG = 8, EVC_LEVEL = 16 };      // k_evtab_scan's columns that a later pass may need
@@ -26,6 +26,14 @@ static int evtab_scan_run(sqg_ctx* c, EventParams& Q, unsigned need) {
         if ((need >> q & 1u) && !cols[q]) { c->err = "k_evtab_scan: a column a later pass reads has no memory"; return SQG_EDEVICE; }
     hipLaunchKernelGGL(k_evtab_scan, dim3((unsigned)Q.bv.n_reads), dim3(CHUNK_WG), 0, c->stream, Q);
     return launched(c, "k_evtab_scan");
+}
+
+// the targets of sqg_batch_align and sqg_batch_scale: every true event's level_raw, the scan pass with that column alone; null without events
+static int evtab_targets(sqg_ctx* c, const BatchView& bv, long long n_events, const int16_t** level_raw) {
+    EventParams Q{bv, (const float2*)nullptr, n_events};
+    const int rc = n_events > 0 ? evtab_scan_run(c, Q, EVC_LEVEL) : SQG_OK;
+    *level_raw = Q.level_raw;
+    return rc;
 }
 
 // workgroups of a flat grid over n_rows rows, one row per lane (k_events_table.h: evtab_for_rows): one trip where the device holds them all

@@ -1,6 +1,6 @@
 // h_scale.h -- sqg_batch_scale, sqg_batch_align_scaled: a per-read shift and scale estimated from the caller's event rows, and the aligner under one
 // Host side of include/sqg_scale.h; included by sqg_hip.hip behind h_collapse.h.  The opening of the checks, the batch's view and the
-// lifetime rule are h_chunks.h's, the scan pass h_events_table.h's, the aligner's body h_align.h's (align_run).
+// lifetime rule are h_chunks.h's, the targets h_events_table.h's, the rows' check and upload and the aligner's body h_align.h's (align_run).
 #pragma once
 
 // k_scale_sums' launch over n rows: `trips` consecutive 64-row trips per wavefront, workgroups of CHUNK_WG / 64 wavefronts, at most 8 of
@@ -26,29 +26,19 @@ extern "C" int sqg_batch_scale(sqg_ctx_t* c, sqg_batch_t* b, const sqg_scale_cfg
     const bool fit = cfg->mode == SQG_SCALE_FIT;
     if (fit && (rc = K.null(in->ev, "in->ev"))) return rc;
     const int n = b->n;
-    if (row_off[0] != 0) return K.bad("row_off must start at 0");
-    for (int i = 0; i < n; i++) {
-        if (row_off[i + 1] < row_off[i]) return K.bad("row_off must not decrease");
-        if (row_off[i + 1] - row_off[i] > 0x7fffffffLL) return K.bad("row_off: a read has 2^31 rows or more");
-    }
-    if ((rc = K.ran(b))) return rc;
+    if ((rc = rows_off_check(K, n, row_off)) || (rc = K.ran(b))) return rc;
     if ((rc = chunk_owned(c, b, who, c->use_dwell_stream)) || n == 0) return rc;
     ScaleScratch& X = c->scale;
-    if ((rc = X.d_off.need(c, (size_t)n + 1)) || (rc = X.d_acc.need(c, (size_t)SCL_COLS * (size_t)n))) return rc;
-    const hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(X.d_off.p, row_off, ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(X.d_acc.p, 0, (size_t)SCL_COLS * (size_t)n * sizeof(unsigned long long), st));
     const BatchView bv = batch_view(c, b);
     ScaleParams P{};
-    P.reads = bv.reads; P.row_off = X.d_off.p; P.n_reads = n; P.n_rows = (long long)row_off[n]; P.n_events = b->n_events;
-    P.sum = (const long long*)in->sum; P.len = in->len; P.ev = (const long long*)in->ev; P.acc = X.d_acc.p;
-    if (P.n_rows > 0) {
-        // the targets: every true event's level_raw (k_events_table.h's scan pass, that column alone), as sqg_batch_align gets it
-        EventParams Q{bv, (const float2*)nullptr, b->n_events};
-        if (b->n_events > 0 && (rc = evtab_scan_run(c, Q, EVC_LEVEL))) return rc;
-        P.level_raw = Q.level_raw;
+    if ((rc = rows_upload(c, bv, row_off, &P.rows)) || (rc = X.d_acc.need(c, (size_t)SCL_COLS * (size_t)n))) return rc;
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipMemsetAsync(X.d_acc.p, 0, (size_t)SCL_COLS * (size_t)n * sizeof(unsigned long long), st));
+    P.n_events = b->n_events; P.sum = (const long long*)in->sum; P.len = in->len; P.ev = (const long long*)in->ev; P.acc = X.d_acc.p;
+    if (P.rows.n_rows > 0) {
+        if ((rc = evtab_targets(c, bv, b->n_events, &P.level_raw))) return rc;      // the targets, as sqg_batch_align gets them
         // pass 1, the sums: over the rows, and for MOMENTS once more over the events
-        const unsigned grid = scale_grid(c, P.n_rows, &P.trips);
+        const unsigned grid = scale_grid(c, P.rows.n_rows, &P.trips);
         if (fit) hipLaunchKernelGGL(k_scale_sums<SCL_FIT>, dim3(grid), dim3(CHUNK_WG), 0, st, P);
         else hipLaunchKernelGGL(k_scale_sums<SCL_ROWS>, dim3(grid), dim3(CHUNK_WG), 0, st, P);
         if ((rc = launched(c, "k_scale_sums"))) return rc;
@@ -62,7 +52,7 @@ extern "C" int sqg_batch_scale(sqg_ctx_t* c, sqg_batch_t* b, const sqg_scale_cfg
     const ScaleOut O{(long long*)out->n, (long long*)out->nx, (long long*)out->sy, (long long*)out->syy, (long long*)out->sx, (long long*)out->sxx,
                      (long long*)out->sxy, out->gain, out->shift, out->rd_dropped};
     const unsigned dgrid = (unsigned)((n + CHUNK_WG - 1) / CHUNK_WG);
-    const int no_rows = P.n_rows == 0;
+    const int no_rows = P.rows.n_rows == 0;
     if (fit) hipLaunchKernelGGL(k_scale_derive<true>, dim3(dgrid), dim3(CHUNK_WG), 0, st, P, O, no_rows);
     else hipLaunchKernelGGL(k_scale_derive<false>, dim3(dgrid), dim3(CHUNK_WG), 0, st, P, O, no_rows);
     if ((rc = launched(c, "k_scale_derive"))) return rc;

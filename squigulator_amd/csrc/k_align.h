@@ -66,7 +66,7 @@ __global__ __launch_bounds__(64) void k_align_forward(AlignParams P) {
     const long long R0 = P.row_off[r];
     const int m = (int)(P.row_off[r + 1] - R0);                   // (below 2^31: the host's check)
     const ReadDesc rd = V.reads[r];
-    const int T = rd.ne0 + max(rd.ne1, 0);
+    const int T = read_events(rd);
     if (m <= 0 || T <= 0) {
         if (lane == 0) { P.end_j[r] = -1; if (P.al_cost) P.al_cost[r] = -1; }
         return;
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(64) void k_align_trace(AlignParams P) {
     const long long R0 = P.row_off[r];
     const int m = (int)(P.row_off[r + 1] - R0);
     const ReadDesc rd = P.bv.reads[r];
-    const int T = rd.ne0 + max(rd.ne1, 0);
+    const int T = read_events(rd);
     int j = P.end_j[r];                                           // the same in every lane
     if (m <= 0 || j < 0) {
         if (P.al_ev) for (int i = lane; i < m; i += 64) P.al_ev[R0 + i] = -1;

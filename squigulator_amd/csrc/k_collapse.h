@@ -2,11 +2,11 @@
 // Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_pileup.h, whose key rule and adds it uses.
 //
 //   k_collapse_rows      a flat grid over the ROWS (evtab_for_rows), one row per lane.  A lane finds its read by a search in the device copy of
-//                        row_off -- one search each for the wavefront's first and last row, and no other when the two agree -- and tests the
-//                        range rule.  A detector over-segments: many consecutive rows go to one event, and raw per-row atomics would pile onto
-//                        one address (profiles/pileup.md).  So the rows are combined within the wavefront first: a lane is a HEAD if its row is
-//                        dropped or its ev differs from the lane before; a ballot of the heads gives every lane its run's first lane, a six-step
-//                        segmented scan over (rows, len, sum, sumsq) the run's sums, and only the LAST lane of a run issues the adds: no-return
+//                        row_off (k_rows.h: rows_read_of) -- one search each for the wavefront's first and last row, and no other when the two
+//                        agree -- and tests the range rule.  A detector over-segments: many consecutive rows go to one event, and raw per-row
+//                        atomics would pile onto one address (profiles/pileup.md).  So the rows are combined within the wavefront first
+//                        (k_rows.h: wave_runs, wave_run_scan): a lane is a HEAD if its row is dropped or its ev differs from the lane before;
+//                        the scan over (rows, len, sum, sumsq) gives the run's sums, and only the LAST lane of a run issues the adds: no-return
 //                        relaxed agent-scope atomics, as in k_pileup.  Runs that cross a wavefront, a workgroup or a trip meet in the atomic:
 //                        integer adds commute, the result does not depend on where the cuts fall.  Dropped rows are counted per read the same
 //                        way (a ballot, one add per run of equal reads), and batch-wide in a register over the wavefront's trips, added once.
@@ -16,62 +16,44 @@
 #pragma once
 
 struct CollapseParams {
-    const ReadDesc* reads;                                    // [n_reads]: a read's events are [ev_off, ev_off + ne0 + max(ne1, 0))
-    const long long* row_off;                                 // [n_reads+1] device copy of the caller's
-    int n_reads;
-    long long n_rows;
+    RowsIn rows;
     const long long *ev, *sum, *sumsq; const int* len;        // the caller's rows; sumsq may be null when ob_sumsq is
     unsigned int* ob_rows; unsigned long long *ob_len, *ob_sum, *ob_sumsq;   // [n_events] the caller's or scratch, zeroed; null: not needed
     int* rd_dropped;                                          // [n_reads] zeroed, may be null
     unsigned long long* dropped;                              // the batch-wide counter, may be null
 };
 
-// the read of row i: the last r in [lo, hi] with row_off[r] <= i (reads without rows are stepped over; row_off[lo] <= i is given)
-__device__ __forceinline__ int collapse_read_of(const long long* row_off, int lo, int hi, const long long i) {
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (row_off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(CHUNK_WG) void k_collapse_rows(CollapseParams P) {
     unsigned long long dropped_here = 0;                      // this wavefront's dropped rows over all its trips (the same in every lane)
-    evtab_for_rows(P.n_rows, [&](const long long i, const bool have, const int lane) {
+    const RowsIn& R = P.rows;
+    const auto off = [&](const int r) { return R.row_off[r]; };
+    evtab_for_rows(R.n_rows, [&](const long long i, const bool have, const int lane) {
         // the wavefront's first and last row (the first lane always has a row when any lane has: the trips start at multiples of 64)
-        const long long w0 = i - lane, w1 = min(w0 + 63, P.n_rows - 1);
+        const long long w0 = i - lane, w1 = min(w0 + 63, R.n_rows - 1);
         int r = 0;
-        if (w0 < P.n_rows) {
-            const int r0 = collapse_read_of(P.row_off, 0, P.n_reads - 1, w0);
-            const int r1 = collapse_read_of(P.row_off, r0, P.n_reads - 1, w1);
-            r = r0 == r1 || !have ? r0 : collapse_read_of(P.row_off, r0, r1, i);
+        if (w0 < R.n_rows) {
+            const int r0 = rows_read_of(off, 0, R.n_reads - 1, w0);
+            const int r1 = rows_read_of(off, r0, R.n_reads - 1, w1);
+            r = r0 == r1 || !have ? r0 : rows_read_of(off, r0, r1, i);
         }
         long long e = -1;
         bool counts = false;
         if (have) {
-            const ReadDesc rd = P.reads[r];
             e = P.ev[i];
-            counts = e >= rd.ev_off && e < rd.ev_off + rd.ne0 + max(rd.ne1, 0);
+            const EventRange own = read_event_range(R.reads[r]);
+            counts = e >= own.lo && e < own.hi;
         }
         // (every lane of the wavefront is here: the ballots and the shuffles below are wave-wide)
         const long long e_up = __shfl_up(e, 1, 64);
         const bool counts_up = __shfl_up((int)counts, 1, 64) != 0;
-        const bool head = !counts || lane == 0 || e != e_up || !counts_up;
-        const unsigned long long heads = __ballot(head);
-        const int first = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));      // the head at or below this lane (lane 0 is one)
-        const bool tail = lane == 63 || (((heads >> 1) >> lane) & 1ull);
+        const auto [first, tail] = wave_runs(!counts || lane == 0 || e != e_up || !counts_up, lane);
         unsigned int v_rows = counts ? 1u : 0u;
         const int ln = counts ? P.len[i] : 0;
         const bool some = ln >= 1;
         unsigned long long v_len = some ? (unsigned long long)ln : 0ull;
         unsigned long long v_sum = some && P.ob_sum ? (unsigned long long)P.sum[i] : 0ull;
         unsigned long long v_sq = some && P.ob_sumsq ? (unsigned long long)P.sumsq[i] : 0ull;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {                                          // the segmented scan: a lane takes what lies inside its run
-            const unsigned int t_rows = __shfl_up(v_rows, d, 64);
-            const unsigned long long t_len = __shfl_up(v_len, d, 64), t_sum = __shfl_up(v_sum, d, 64), t_sq = __shfl_up(v_sq, d, 64);
-            if (lane - d >= first) { v_rows += t_rows; v_len += t_len; v_sum += t_sum; v_sq += t_sq; }
-        }
+        wave_run_scan(first, lane, v_rows, v_len, v_sum, v_sq);
         if (counts && tail) {
             if (P.ob_rows) __hip_atomic_fetch_add(P.ob_rows + e, v_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (P.ob_len) __hip_atomic_fetch_add(P.ob_len + e, v_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

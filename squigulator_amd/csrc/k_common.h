@@ -168,6 +168,11 @@ struct ReadDesc {
                           // several partitions with SigParams.evrec32: the read's link, -1 if it is cut into pieces of several links
 };
 
+// the events of a read: how many (segment 1 is absent where ne1 < 0), and the half-open range they take in the batch's event arrays
+struct EventRange { long long lo, hi; };
+__device__ __forceinline__ int read_events(const ReadDesc& rd) { return rd.ne0 + max(rd.ne1, 0); }
+__device__ __forceinline__ EventRange read_event_range(const ReadDesc& rd) { return {rd.ev_off, rd.ev_off + read_events(rd)}; }
+
 struct FixEntry {         // one sample handed to the FP64 path
     long long at;         // absolute index into the signal slab
     long long ev;         // batch-wide event index (k-mer recomputed from the bases)

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_evtab_scan(EventParams Q) {
     const int r = blockIdx.x;
     const ReadDesc rd = V.reads[r];
     const long long n = V.sig_off[r + 1] - V.sig_off[r];
-    const int ne0 = rd.ne0, ne = rd.ne0 + max(rd.ne1, 0), kind = V.kind;
+    const int ne0 = rd.ne0, ne = read_events(rd), kind = V.kind;
     const SegRanges sr = seg_ranges(V, rd);
     const int a = sr.a, b = sr.b;
     const uint8_t* bp0 = V.bases + rd.base_off;

@@ -1,5 +1,5 @@
 // k_scale.h -- per-read sums of the caller's event rows and of the read's targets, and the shift / scale estimate from them (include/sqg_scale.h)
-// Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_collapse.h, whose route for rows it takes.
+// Part of the device code of the per-read signal path; included through sqg_kernels.h behind k_collapse.h; the rows are k_rows.h's.
 //
 //   k_scale_sums<KIND>   a flat grid over the ROWS (SCL_ROWS, SCL_FIT) or over the batch's EVENTS (SCL_TARGETS: the same reduction, a read's
 //                        events in place of its rows), one row per lane, 64 rows per wavefront trip.  The grid is CAPPED (h_scale.h:
@@ -8,9 +8,9 @@
 //                        the end of the read the wavefront is in; a search in the offsets only when it fails) every lane adds its row to
 //                        accumulators it keeps in registers over the trips; when the read changes, and at the end, the wavefront reduces
 //                        them and lane 0 issues ONE set of 64-bit integer adds to the read's sums (profiles/pileup.md, profiles/collapse.md:
-//                        a counter that every row hits is what to avoid).  A trip that holds a read boundary is combined by k_collapse_rows'
-//                        segmented scan, a segment being a run of lanes of one read, and the last lane of every segment adds.  Integer adds
-//                        commute: no sum depends on where the cuts fall or on arrival order.  No-return relaxed agent-scope atomics.
+//                        a counter that every row hits is what to avoid).  A trip that holds a read boundary is combined by the run
+//                        combination of k_rows.h (wave_runs, wave_run_part), a run being the lanes of one read, and the last lane of every run
+//                        adds.  Integer adds commute: no sum depends on where the cuts fall or on arrival order.  No-return relaxed agent-scope atomics.
 //                        The row value needs no 64-bit integer division: for |16 sum| < 2^52 the double quotient is within one of the
 //                        floor and is corrected by the remainder; beyond, |16 sum / len| > 2^20 whatever len < 2^31 is, and the clamp decides.
 //                        SCL_FIT gathers level_raw[ev[i]]: 2 B per row, any order of ev.
@@ -21,10 +21,8 @@ enum { SCL_N, SCL_SY, SCL_SYY, SCL_SX, SCL_SXX, SCL_SXY, SCL_DROP, SCL_COLS };  
 enum { SCL_ROWS, SCL_TARGETS, SCL_FIT };                                             // k_scale_sums' kinds
 
 struct ScaleParams {
-    const ReadDesc* reads;                                    // [n_reads]: a read's events are [ev_off, ev_off + ne0 + max(ne1, 0))
-    const long long* row_off;                                 // [n_reads+1] device copy of the caller's
-    int n_reads;
-    long long n_rows, n_events;
+    RowsIn rows;
+    long long n_events;
     long long trips;                                          // 64-row trips a wavefront makes, one behind the other
     const long long *sum, *ev; const int* len;                // the caller's rows; ev: SCL_FIT only
     const int16_t* level_raw;                                 // [n_events] k_evtab_scan's column (scratch)
@@ -34,23 +32,6 @@ struct ScaleParams {
 struct ScaleOut {                                             // the caller's, [n_reads], any may be null
     long long *n, *nx, *sy, *syy, *sx, *sxx, *sxy; int *gain, *shift, *rd_dropped;
 };
-
-// the first row (SCL_TARGETS: event) of read r, r = n_reads: their number
-template <int KIND>
-__device__ __forceinline__ long long scale_off(const ScaleParams& P, const int r) {
-    if (KIND == SCL_TARGETS) return r < P.n_reads ? P.reads[r].ev_off : P.n_events;
-    return P.row_off[r];
-}
-
-// the read of row i: the last r in [lo, hi] whose first row is <= i (reads without rows are stepped over; that of lo is <= i)
-template <int KIND>
-__device__ __forceinline__ int scale_read_of(const ScaleParams& P, int lo, int hi, const long long i) {
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (scale_off<KIND>(P, mid) <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // y of a row: clamp(floor(16 sum / max(len, 1)), -2^20, 2^20), the product modulo 2^64
 __device__ __forceinline__ long long scale_row_value(const long long s, const int len) {
@@ -76,7 +57,7 @@ __device__ __forceinline__ void scale_flush(const ScaleParams& P, unsigned long 
         unsigned long long v = a[k];
 #pragma unroll
         for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-        if (lane == 0 && v) __hip_atomic_fetch_add(P.acc + (long long)scale_col<KIND>(k) * P.n_reads + cur, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0 && v) __hip_atomic_fetch_add(P.acc + (long long)scale_col<KIND>(k) * P.rows.n_reads + cur, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         a[k] = 0;
     }
 }
@@ -84,8 +65,11 @@ __device__ __forceinline__ void scale_flush(const ScaleParams& P, unsigned long 
 template <int KIND>
 __global__ __launch_bounds__(CHUNK_WG) void k_scale_sums(ScaleParams P) {
     constexpr int N = scale_cols<KIND>();
+    const RowsIn& R = P.rows;
     const int lane = threadIdx.x & 63;
-    const long long n = KIND == SCL_TARGETS ? P.n_events : P.n_rows;
+    const long long n = KIND == SCL_TARGETS ? P.n_events : R.n_rows;
+    // the first row (SCL_TARGETS: event) of read r, r = n_reads: their number
+    const auto off = [&](const int r) { return KIND != SCL_TARGETS ? R.row_off[r] : r < R.n_reads ? R.reads[r].ev_off : P.n_events; };
     const long long wave = (long long)blockIdx.x * (CHUNK_WG / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long long span = 64 * P.trips;
     const long long end = min((wave + 1) * span, n);              // this wavefront's rows: [wave * span, end)
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(CHUNK_WG) void k_scale_sums(ScaleParams P) {
 #pragma unroll
     for (int k = 0; k < N; k++) a[k] = 0;
     int cur = -1;                                                 // the read the accumulators belong to (the same in every lane)
-    long long cur_end = 0, cur_e0 = 0, cur_e1 = 0;                // the end of its rows; SCL_FIT: its events
+    long long cur_end = 0; EventRange cur_ev{0, 0};               // the end of its rows; SCL_FIT: its events
     for (long long base = wave * span; base < end; base += 64) {
         const long long i = base + lane;
         const bool have = i < end;
@@ -101,15 +85,15 @@ __global__ __launch_bounds__(CHUNK_WG) void k_scale_sums(ScaleParams P) {
         bool one = cur >= 0 && w1 < cur_end;                      // the trip lies inside read `cur`
         int r = cur;
         if (!one) {
-            const int r0 = scale_read_of<KIND>(P, max(cur, 0), P.n_reads - 1, base);
-            const int r1 = scale_read_of<KIND>(P, r0, P.n_reads - 1, w1);
+            const int r0 = rows_read_of(off, max(cur, 0), R.n_reads - 1, base);
+            const int r1 = rows_read_of(off, r0, R.n_reads - 1, w1);
             scale_flush<KIND>(P, a, cur, lane);
             if (r0 == r1) {
-                one = true; r = cur = r0; cur_end = scale_off<KIND>(P, r0 + 1);
-                if (KIND == SCL_FIT) { const ReadDesc rd = P.reads[r0]; cur_e0 = rd.ev_off; cur_e1 = rd.ev_off + rd.ne0 + max(rd.ne1, 0); }
+                one = true; r = cur = r0; cur_end = off(r0 + 1);
+                if (KIND == SCL_FIT) cur_ev = read_event_range(R.reads[r0]);
             } else {
                 cur = -1;
-                r = have ? scale_read_of<KIND>(P, r0, r1, i) : r1;                             // (the lanes behind the last row: the last segment, zeros)
+                r = have ? rows_read_of(off, r0, r1, i) : r1;                                  // (the lanes behind the last row: the last run, zeros)
             }
         }
         unsigned long long t[N];
@@ -123,10 +107,9 @@ __global__ __launch_bounds__(CHUNK_WG) void k_scale_sums(ScaleParams P) {
                 const long long y = scale_row_value(P.sum[i], P.len[i]);
                 t[0] = (unsigned long long)y; t[1] = (unsigned long long)(y * y);
             } else {
-                long long e0 = cur_e0, e1 = cur_e1;
-                if (!one) { const ReadDesc rd = P.reads[r]; e0 = rd.ev_off; e1 = rd.ev_off + rd.ne0 + max(rd.ne1, 0); }
+                const EventRange mine = one ? cur_ev : read_event_range(R.reads[r]);
                 const long long e = P.ev[i];
-                if (e >= e0 && e < e1) {
+                if (e >= mine.lo && e < mine.hi) {
                     const long long y = scale_row_value(P.sum[i], P.len[i]);
                     const long long x = 16 * (long long)P.level_raw[e];
                     t[0] = 1; t[1] = (unsigned long long)y; t[2] = (unsigned long long)(y * y);
@@ -139,23 +122,18 @@ __global__ __launch_bounds__(CHUNK_WG) void k_scale_sums(ScaleParams P) {
             for (int k = 0; k < N; k++) a[k] += t[k];
             continue;
         }
-        // a read boundary inside the trip (every lane of the wavefront is here): a segment is a run of lanes of one read
+        // a read boundary inside the trip (every lane of the wavefront is here): a run is the lanes of one read
         const int r_up = __shfl_up(r, 1, 64);
-        const unsigned long long heads = __ballot(lane == 0 || r != r_up);
-        const int first = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));                // the head at or below this lane (lane 0 is one)
-        const bool tail = lane == 63 || (((heads >> 1) >> lane) & 1ull);
+        const auto [first, tail] = wave_runs(lane == 0 || r != r_up, lane);
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {                                                    // the segmented scan: a lane takes what lies inside its segment
+        for (int d = 1; d < 64; d <<= 1) {                                                    // wave_run_scan's steps over the array
 #pragma unroll
-            for (int k = 0; k < N; k++) {
-                const unsigned long long u = __shfl_up(t[k], d, 64);
-                if (lane - d >= first) t[k] += u;
-            }
+            for (int k = 0; k < N; k++) t[k] += wave_run_part(t[k], d, lane - d >= first);
         }
         if (tail) {
 #pragma unroll
             for (int k = 0; k < N; k++)
-                if (t[k]) __hip_atomic_fetch_add(P.acc + (long long)scale_col<KIND>(k) * P.n_reads + r, t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t[k]) __hip_atomic_fetch_add(P.acc + (long long)scale_col<KIND>(k) * R.n_reads + r, t[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     scale_flush<KIND>(P, a, cur, lane);
@@ -195,11 +173,12 @@ __device__ __forceinline__ void scale_estimate(const long long n, const long lon
 template <bool FIT>
 __global__ __launch_bounds__(CHUNK_WG) void k_scale_derive(ScaleParams P, ScaleOut O, int no_rows) {
     const int r = blockIdx.x * CHUNK_WG + threadIdx.x;
-    if (r >= P.n_reads) return;
-    const auto col = [&](const int c) { return (long long)P.acc[(long long)c * P.n_reads + r]; };
-    const ReadDesc rd = P.reads[r];
-    const long long n = FIT ? col(SCL_N) : P.row_off[r + 1] - P.row_off[r];
-    const long long nx = FIT ? n : no_rows ? 0 : rd.ne0 + max(rd.ne1, 0);
+    const RowsIn& R = P.rows;
+    if (r >= R.n_reads) return;
+    const auto col = [&](const int c) { return (long long)P.acc[(long long)c * R.n_reads + r]; };
+    const ReadDesc rd = R.reads[r];
+    const long long n = FIT ? col(SCL_N) : R.row_off[r + 1] - R.row_off[r];
+    const long long nx = FIT ? n : no_rows ? 0 : read_events(rd);
     const long long sy = col(SCL_SY), syy = col(SCL_SYY), sx = col(SCL_SX), sxx = col(SCL_SXX), sxy = col(SCL_SXY);
     int gain, shift;
     scale_estimate<FIT>(n, nx, sy, syy, sx, sxx, sxy, &gain, &shift);

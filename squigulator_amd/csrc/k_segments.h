@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64) void k_segments(SegParams Q) {
         s1 = seg_wave_sum(sa); s2 = s3 = seg_wave_sum(sb);
         v.ev0 = b; v.nev = rd.ne0 - b; v.base0 = b;
     } else if (V.kind == SEG_RNA) {
-        const int i1 = a, i2 = b, ne = rd.ne0 + max(rd.ne1, 0);
+        const int i1 = a, i2 = b, ne = read_events(rd);
         long long pa = 0, ad = 0, st = 0;                   // samples of poly-A, adaptor, stall
         for (int e = i1 + lane; e < ne; e += 64) {
             const long long x = d ? (long long)d[e] : sps;

@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_align.h, k_collapse.h and k_scale.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_rows.h, k_align.h, k_collapse.h and k_scale.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -58,6 +58,7 @@
 #include "k_events_table.h"
 #include "k_pileup.h"
 #include "k_detect.h"
+#include "k_rows.h"
 #include "k_align.h"
 #include "k_collapse.h"
 #include "k_scale.h"

@@ -1,5 +1,5 @@
 """The calls that read a finished batch on the device share scratch of the context (the reads' constants, the inserts' spans, the chunk
-and site plans, the event columns, the detector's plan, the aligner's levels): what a call writes must not depend on which other calls
+and site plans, the event columns, the detector's plan, the aligner's levels, the caller's row offsets): what a call writes must not depend on which other calls
 ran before it on that context.  Every call alone on a fresh context is the reference; the same calls in the listed order, in reverse,
 and across two consecutive batches -- those for batch 0 made after batch 1 has run, while batch 0 still owns its device results --
 must give the same tensors, bit for bit."""
@@ -41,6 +41,43 @@ def _align_truth(b):
     return b.align(b.ev_off, ev.sum[idx].contiguous(), ev.ev_len[idx].contiguous(), (256, 1024, 16384))
 
 
+def _detected_rows(b, preset):
+    """(row_off, ev, sum, sumsq, len): the detected rows of a preset, assigned to events by the detector's own true_ev"""
+    dt = b.detect(preset, outputs=("sum", "sumsq", "dt_len", "true_ev"))
+    return dt.det_off, dt.true_ev, dt.sum, dt.sumsq, dt.dt_len
+
+
+def _truth_rows(b, rna):
+    """(row_off, ev, sum, sumsq, len): the true table's own rows, every read's in stored-sample order like _align_truth, each assigned to itself"""
+    ev = b.events(outputs=("sum", "sumsq", "ev_len"))
+    idx = torch.from_numpy(stored_order(b.ev_off, rna)).to(ev.sum.device)
+    return b.ev_off, idx, ev.sum[idx].contiguous(), ev.sumsq[idx].contiguous(), ev.ev_len[idx].contiguous()
+
+
+def _scale_fit_detected(b):
+    off, ev, s, _, ln = _detected_rows(b, "dna")
+    return b.scale(off, s, ln, ev=ev, mode="fit")
+
+
+def _align_scaled_truth(b):
+    """the truth rows aligned under the scaling estimated from the detected ones: the two calls' row_off differ"""
+    est = _scale_fit_detected(b)
+    off, _, s, _, ln = _truth_rows(b, False)
+    return b.align(off, s, ln, scale=(est.gain, est.shift))
+
+
+def _scale_moments_truth(b):
+    off, _, s, _, ln = _truth_rows(b, True)
+    return b.scale(off, s, ln, mode="moments")
+
+
+def _pileup_rows(b, rows, **kw):
+    p = b.gen.new_pileup(**kw)
+    counted, outside, unseen, dropped = b.pileup_rows(p, *rows)
+    return api.Chunks(counted=counted, outside=outside, unseen=unseen, dropped=dropped, row_off=np.asarray(rows[0]),
+                      **{n: getattr(p, n) for n in api.PILEUP_OUTPUTS})
+
+
 def _origin(b):
     """one origin per read, the second on the minus strand; the window [200, 4000) leaves events of every read outside"""
     n = b.n_reads
@@ -57,6 +94,10 @@ JOBS = {
         ("events medmad", lambda b: b.events("medmad")),
         ("align detected", _align_detected),
         ("events pa", lambda b: b.events("pa")),
+        # the caller's rows, whose offsets share one scratch array: neighbours take rows of different row_off (detected, truth, detected)
+        ("scale fit detected", _scale_fit_detected),
+        ("align scaled truth", _align_scaled_truth),
+        ("collapse detected medmad", lambda b: b.collapse(*_detected_rows(b, "dna"), norm="medmad")),
         ("pileup ref medmad", lambda b: _pileup(b, origin=_origin(b), by="ref", norm="medmad", lo=200, hi=4000)),
     ],
     # RNA, SQG_PREFIX
@@ -70,6 +111,10 @@ JOBS = {
         ("detect pa", lambda b: b.detect("rna")),
         ("events medmad", lambda b: b.events("medmad", trim=False)),
         ("pileup kmer trim", lambda b: _pileup(b, by="kmer", norm="medmad", trim=True)),
+        # (truth, detected, truth)
+        ("scale moments truth", _scale_moments_truth),
+        ("collapse detected trim", lambda b: b.collapse(*_detected_rows(b, "rna"), norm="medmad", trim=True)),
+        ("pileup_rows kmer trim truth", lambda b: _pileup_rows(b, _truth_rows(b, True), by="kmer", norm="medmad", trim=True)),
     ],
 }
 
@@ -164,6 +209,10 @@ def test_outputs_do_not_depend_on_the_calls_before(cid, mode):
             continue
         assert any(isinstance(t, torch.Tensor) and (t.shape != getattr(a1, k).shape or not torch.equal(t, getattr(a1, k))) for k, t in vars(a0).items()), name
     assert alone[(0, calls[-1][0])].counted > 0
+    # neighbouring calls that take rows take different ones, detected against truth: offsets left in the scratch by one would change the other
+    taken = [getattr(alone[(0, name)], "row_off", None) for name, _ in calls]
+    pairs = [(a, b) for a, b in zip(taken, taken[1:]) if a is not None and b is not None]
+    assert len(pairs) >= 2 and all(not np.array_equal(a, b) for a, b in pairs), cid
     if cid == "r9_meth":
         assert alone[(0, "pileup ref medmad")].outside > 0
     else:                                                  # the trimmed job took the inserts' spans: the same sums, other statistics
