@@ -90,7 +90,7 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
-             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS", "SQG_TEST_SCALE_GRID")
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS", "SQG_TEST_SCALE_GRID", "SQG_TEST_CALL_GRID")
 
 # include/sqg_chunks.h: bound by load_library only when the library has them (the CPU backend does not)
 EXPORTS_CHUNKS = ("sqg_chunk_plan", "sqg_batch_chunks")
@@ -230,6 +230,38 @@ class CAlignScale(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("gain", "shift")]
 
 
+# include/sqg_call.h: bound the same way
+EXPORTS_CALL = ("sqg_call_plan", "sqg_batch_call")
+CALL_NEIGH_READ, CALL_NEIGH_SAME = 0, 1
+CALL_DEFAULT = (CALL_NEIGH_SAME, 256 * 50, 256 * 2, 1)         # SQG_CALL_DEFAULT
+CALL_OUTPUTS = ("site_read", "site_pos", "label", "site_key", "n_obs", "nll_c", "nll_m", "llr", "call")
+CALL_FREQ = ("cov", "truth", "called", "meth")
+
+
+class CCallCfg(C.Structure):
+    _fields_ = [("neigh", C.c_uint32), ("term_cap", C.c_int32), ("llr_min", C.c_int32), ("min_obs", C.c_int32)]
+
+
+class CCallIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("sum", "len64", "len32")]
+
+
+class CCallModel(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w", "c")]
+
+
+class CCallOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in CALL_OUTPUTS]
+
+
+class CCallFreq(C.Structure):
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64)] + [(n, C.c_void_p) for n in CALL_FREQ]
+
+
+class CCallStat(C.Structure):
+    _fields_ = [("sites", C.c_int64), ("outside", C.c_int64), ("called", C.c_int64), ("agree", C.c_int64)]
+
+
 # include/sqg_collapse.h: bound the same way
 EXPORTS_COLLAPSE = ("sqg_batch_collapse", "sqg_batch_pileup_rows")
 COLLAPSE_INPUTS = ("ev", "sum", "sumsq", "len")
@@ -261,6 +293,15 @@ class Pileup:
         self.__dict__.update(kw)
 
 
+class CallFreq:
+    """What SignalGenerator.new_call_freq() returns: the key window [lo, hi) and the four sums Batch.call(freq=...) adds to, torch tensors
+    [hi - lo] on the context's device (uint32 bit patterns in int32 tensors; include/sqg_call.h says what they hold)"""
+
+    def __init__(self, lo, hi, **kw):
+        self.lo, self.hi = lo, hi
+        self.__dict__.update(kw)
+
+
 class Chunks:
     """What Batch.chunks() returns: torch tensors on the context's device (include/sqg_chunks.h says what they hold)"""
 
@@ -279,6 +320,8 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_PILEUP, {"sqg_batch_pileup": (CPileupCfg, COrigin, CPileupOut, CPileupStat)}),
     (EXPORTS_DETECT, {"sqg_detect_plan": (CDetectCfg,) + _PLAN, "sqg_batch_detect": (CDetectCfg, CDetectOut)}),
     (EXPORTS_ALIGN, {"sqg_batch_align": (CAlignCfg, C.c_int64, CAlignIn, CAlignOut)}),
+    (EXPORTS_CALL, {"sqg_call_plan": _PLAN,
+                    "sqg_batch_call": (CCallCfg, CCallIn, CCallModel, CAlignScale, COrigin, CCallOut, CCallFreq, CCallStat)}),
     (EXPORTS_SCALE, {"sqg_batch_scale": (CScaleCfg, C.c_int64, CScaleIn, CScaleOut),
                      "sqg_batch_align_scaled": (CAlignCfg, C.c_int64, CAlignIn, CAlignScale, CAlignOut)}),
     (EXPORTS_COLLAPSE, {"sqg_batch_collapse": (CCollapseCfg, C.c_int64, CCollapseIn, CCollapseOut),
@@ -286,7 +329,8 @@ _CONSUMER_EXPORTS = (
 )
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
-          "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}, "mode": {"moments": SCALE_MOMENTS, "fit": SCALE_FIT}}
+          "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}, "mode": {"moments": SCALE_MOMENTS, "fit": SCALE_FIT},
+          "neigh": {"read": CALL_NEIGH_READ, "same": CALL_NEIGH_SAME}}
 
 
 def _enum(who, **given):
@@ -561,7 +605,7 @@ class Batch:
         self._call(name, C.byref(cfg), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total))
         return off, int(total.value)
 
-    def _table(self, name, args, struct, names, shapes, want, **head):
+    def _table(self, name, args, struct, names, shapes, want, tail=(), **head):
         """what sites / events / detect / align share: the Chunks of `head` and, for every output name, a zeroed tensor of its
         (shape, dtype) in `shapes` if it is wanted, else None; then the library's `name` with `args` and the C struct of their addresses"""
         import torch
@@ -569,7 +613,7 @@ class Batch:
         ch = Chunks(**head, **{n: (torch.zeros(shapes[n][0], dtype=shapes[n][1], device=dev) if n in want else None) for n in names})
         out = _ptrs(struct, (getattr(ch, n) for n in names))
         torch.cuda.synchronize(dev)                         # (the zero fills and the caller's own work on its inputs, before another stream touches the blocks)
-        self._call(name, *args, C.byref(out))
+        self._call(name, *args, C.byref(out), *tail)
         return ch
 
     def run(self):
@@ -937,6 +981,68 @@ class Batch:
         return self._table("sqg_batch_collapse", (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin)), CCollapseOut, COLLAPSE_OUTPUTS, shapes, want,
                            n_rows=nr, row_off=off, n_events=ne)
 
+    def call_plan(self):
+        """(site_off [n_reads+1], n_sites): the first CpG site of every read as Batch.call() numbers them (sqg_call_plan, include/sqg_call.h;
+        device work and a copy-back of the per-read counts)"""
+        _need(self.gen.L, "sqg_call_plan", "sqg_call.h", "call")
+        off, total = np.zeros(self.n_reads + 1, np.int64), C.c_int64()
+        self._call("sqg_call_plan", off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total))
+        return off, int(total.value)
+
+    def call(self, sum, len, model=None, scale=None, origin=None, freq=None, outputs=None, **cfg) -> Chunks:       # noqa: A002  (the header's names)
+        """Per-read CpG methylation calls of the batch, scored on the device from one row of (sum, len) per row of Batch.events()
+        (sqg_batch_call, include/sqg_call.h): the events whose k-mer holds a CpG's C are scored under the pore model's rows with C and with
+        M there, in exact integers.  sum (int64) and len (int32: Batch.events()'s ev_len; or int64: Batch.collapse()'s ob_len, an event
+        with len < 1 is unobserved): torch tensors of n_events elements on the context's device.  model=(w, c): int32 tensors [5^k]
+        (default SignalGenerator.call_model()).  scale=(gain, shift) as in Batch.align().  origin=(key0, step) as in Batch.pileup()
+        (default: the sampler's).  freq: a CallFreq of SignalGenerator.new_call_freq(), added to.  cfg by keyword: neigh ("same" | "read"),
+        term_cap, llr_min, min_obs (default SQG_CALL_DEFAULT).  torch tensors [n_sites]: site_read, site_pos (int32), label (uint8),
+        site_key (int64), n_obs, nll_c, nll_m, llr (int32, 1/256 nat; llr > 0 speaks for M), call (uint8: 0 none, 1 unmethylated,
+        2 methylated); site_off (numpy, [n_reads+1]) and n_sites from the plan; stat = (sites, outside, called, agree).
+        outputs: the names wanted (default all, site_key only where there is an origin); the others are None."""
+        import torch
+        _need(self.gen.L, "sqg_batch_call", "sqg_call.h", "call")
+        if set(cfg) - {"neigh", "term_cap", "llr_min", "min_obs"}:
+            raise SqgError(-1, "call", f"unknown cfg {sorted(set(cfg) - {'neigh', 'term_cap', 'llr_min', 'min_obs'})}")
+        ng, = _enum("call", neigh=cfg.get("neigh", CALL_DEFAULT[0]))
+        c = CCallCfg(ng, *(int(cfg.get(n, d)) for n, d in zip(("term_cap", "llr_min", "min_obs"), CALL_DEFAULT[1:])))
+        dev = torch.device("cuda", self.gen.device)
+        ne = self._n_events()
+        keep = torch.zeros(1, dtype=torch.int64, device=dev)    # (a valid address for an empty table: NULL is an error, and nothing is read)
+
+        def addr(name, t, dts, n):
+            if not (isinstance(t, torch.Tensor) and t.dtype in dts and t.device == dev and t.is_contiguous() and t.numel() >= n):
+                raise SqgError(-1, "call", f"{name} must be a contiguous {' or '.join(str(d) for d in dts)} tensor of at least {n} elements on {dev}")
+            return t.data_ptr() if t.numel() else keep.data_ptr()
+        a_sum, a_len = addr("sum", sum, (torch.int64,), ne), addr("len", len, (torch.int32, torch.int64), ne)
+        cin = CCallIn(a_sum, a_len if len.dtype == torch.int64 else None, a_len if len.dtype == torch.int32 else None)
+        if model is None:
+            model = self.gen.call_model()
+        if isinstance(model, torch.Tensor) or _len(model) != 2:
+            raise SqgError(-1, "call", "model must be (w, c)")
+        rows = 5 ** self.gen.kmer_size
+        cmod = CCallModel(*(addr(f"model: {n}", t, (torch.int32,), rows) for n, t in zip(("w", "c"), model)))
+        csc = None
+        if scale is not None:
+            if isinstance(scale, torch.Tensor) or _len(scale) != 2:
+                raise SqgError(-1, "call", "scale must be (gain, shift)")
+            csc = CAlignScale(*(addr(f"scale: {n}", t, (torch.int32,), self.n_reads) for n, t in zip(("gain", "shift"), scale)))
+        org, held = self._origin("call", origin)
+        keyed = origin is not None or hasattr(self, "sampled")
+        want = _want(outputs, CALL_OUTPUTS, "call") if outputs is not None or keyed else set(CALL_OUTPUTS) - {"site_key"}
+        cfq = None
+        if freq is not None:
+            cfq = CCallFreq(int(freq.lo), int(freq.hi), *(t.data_ptr() if t is not None and t.numel() else None for t in (getattr(freq, n) for n in CALL_FREQ)))
+        off, ns = self.call_plan()
+        st = CCallStat()
+        dts = dict(site_read=torch.int32, site_pos=torch.int32, label=torch.uint8, site_key=torch.int64, n_obs=torch.int32, nll_c=torch.int32,
+                   nll_m=torch.int32, llr=torch.int32, call=torch.uint8)
+        ref = lambda s: C.byref(s) if s is not None else None     # noqa: E731
+        ch = self._table("sqg_batch_call", (C.byref(c), C.byref(cin), C.byref(cmod), ref(csc), ref(org)), CCallOut, CALL_OUTPUTS,
+                         {n: (ns, dt) for n, dt in dts.items()}, want, tail=(ref(cfq), C.byref(st)), n_sites=ns, site_off=off)
+        ch.stat = (int(st.sites), int(st.outside), int(st.called), int(st.agree))
+        return ch
+
     def _origin(self, who, origin):
         """the C origin of pileup() / pileup_rows() (None: the sampler's) and the arrays it points into"""
         if origin is None:
@@ -1139,6 +1245,38 @@ class SignalGenerator:
         dev = torch.device("cuda", self.device)
         return Pileup(cfg, planes, **{n: (torch.zeros((planes, hi - lo), dtype=torch.int32 if n == "n" else torch.int64, device=dev) if n in want else None)
                                       for n in PILEUP_OUTPUTS})
+
+    def new_call_freq(self, lo: int | None = None, hi: int | None = None, outputs=None) -> CallFreq:
+        """A zeroed called-frequency table for Batch.call(freq=...) (include/sqg_call.h): torch tensors [hi - lo] on the context's device --
+        cov, truth, called, meth (uint32 bit patterns in int32 tensors) -- keyed by the forward-strand coordinate of a CpG's C.  [lo, hi):
+        default the whole loaded genome.  outputs: the names wanted (default all); the others are None."""
+        import torch
+        _need(self.L, "sqg_batch_call", "sqg_call.h", "call")
+        want = _want(outputs, CALL_FREQ, "call")
+        lo = 0 if lo is None else int(lo)
+        if hi is None:
+            if getattr(self, "genome_len", None) is None:
+                raise SqgError(-1, "call", "new_call_freq without hi= needs a loaded genome")
+            hi = self.genome_len
+        if hi < lo:
+            raise SqgError(-1, "call", "hi must not be below lo")
+        dev = torch.device("cuda", self.device)
+        return CallFreq(lo, int(hi), **{n: (torch.zeros(int(hi) - lo, dtype=torch.int32, device=dev) if n in want else None) for n in CALL_FREQ})
+
+    def call_model(self):
+        """(w, c): the recommended model tables of include/sqg_call.h from the context's own pore model, int32 tensors [5^k] on the
+        context's device: sdc = level_stdv * digitisation / range in doubles, w = clip(rint(2^24 / (2 sdc sdc)), 0, 2^24),
+        c = clip(rint(256 ln(sdc)), +-2^20).  Made once per context."""
+        import torch
+        if getattr(self, "_call_model", None) is None:
+            stdv = np.frombuffer(self._model, dtype=np.float32).reshape(-1, 2)[:, 1].astype(np.float64)
+            sdc = stdv * np.float64(self.profile.digitisation) / np.float64(self.profile.range)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                w = np.nan_to_num(np.clip(np.rint(float(1 << 24) / (2.0 * sdc * sdc)), 0, 1 << 24), nan=0.0)
+                c = np.nan_to_num(np.clip(np.rint(256.0 * np.log(sdc)), -(1 << 20), 1 << 20), nan=0.0)
+            dev = torch.device("cuda", self.device)
+            self._call_model = tuple(torch.from_numpy(a.astype(np.int32)).to(dev) for a in (w, c))
+        return self._call_model
 
     def pinned(self, nbytes: int, dtype=np.uint8) -> np.ndarray:
         """A page-locked host array (sqg_host_alloc) for fast sqg_fetch_* destinations; freed with the generator."""

@@ -179,6 +179,16 @@ struct ScaleScratch {
     void release() { *this = ScaleScratch(); }
 };
 
+// device scratch of sqg_call_plan and sqg_batch_call (h_call.h): the plan (k_call_scan<0>'s counts), the per-site records, the counters
+struct CallScratch {
+    ReadPlan plan;
+    DevBuf<int2> d_rec;                                        // [n_sites] {p, read} (k_call_scan<1> -> k_call_score)
+    DevBuf<uint8_t> d_skip;                                    // [n_reads] the batch's reads shorter than a k-mer
+    DevBuf<unsigned long long> d_stat;                         // {outside, called, agree}
+    const void* plan_of = nullptr; unsigned long long plan_run = 0;   // the batch (and its run index) the plan was last made for
+    void release() { *this = CallScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -322,6 +332,7 @@ struct sqg_ctx {
     AlignScratch align;                                        // sqg_batch_align (h_align.h)
     CollapseScratch collapse;                                  // sqg_batch_collapse, sqg_batch_pileup_rows (h_collapse.h)
     ScaleScratch scale;                                        // sqg_batch_scale (h_scale.h)
+    CallScratch call;                                          // sqg_call_plan, sqg_batch_call (h_call.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

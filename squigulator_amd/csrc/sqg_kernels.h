@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_rows.h, k_align.h, k_collapse.h and k_scale.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_rows.h, k_align.h, k_collapse.h, k_scale.h and k_call.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -29,6 +29,9 @@
 //                 atomic per run -- mean / sd of those sums, and their pileup under k_pileup's rules (include/sqg_collapse.h)
 //   k_scale_*     per-read sums of the caller's rows and of the read's targets -- in registers over a wavefront's consecutive trips, one set of integer
 //                 atomics per wavefront and read -- and the shift / scale estimate from them in FP64 (include/sqg_scale.h)
+//   k_call_*      the CpG sites of every read from 16-byte loads of its bases, ranked by k_chunks.h's scan, then per site the base-5 ranks of its span's
+//                 k-mers under C and under M, the two rows' levels against the caller's event sums in exact integers, the call, and the adds to a
+//                 called frequency per position by no-return integer atomics (include/sqg_call.h)
 //   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
@@ -62,3 +65,4 @@
 #include "k_align.h"
 #include "k_collapse.h"
 #include "k_scale.h"
+#include "k_call.h"
