@@ -48,8 +48,11 @@ def ev_offsets(reads, k):
     return np.concatenate(([0], np.cumsum([len(r) - k + 1 if len(r) >= k else 5 for r in reads]))).astype(np.int64)
 
 
+TERM_CAPS, LLR_MINS, MIN_OBS = [0, 1, 300, 256 * 50, 1 << 26], [0, 1, 512, 40000], [0, 1, 3, 12]
+
+
 def drawn_cfg(rng):
-    return (int(rng.integers(0, 2)), int(rng.choice([0, 1, 300, 256 * 50, 1 << 26])), int(rng.choice([0, 1, 512, 40000])), int(rng.choice([0, 1, 3, 12])))
+    return (int(rng.integers(0, 2)), int(rng.choice(TERM_CAPS)), int(rng.choice(LLR_MINS)), int(rng.choice(MIN_OBS)))
 
 
 def drawn_rows(rng, n_events, level_raw=None, wild=True):

@@ -3,6 +3,8 @@ k, a model, batches of staged reads and the cfg of every consumer call -- drawn 
 table holds by construction; and facts(su): what the oracle and the numpy references alone say of such a case.  Not collected."""
 import numpy as np
 
+import call_cases as CS
+import call_ref as CL
 import chunks_ref as R
 import shard_cases as SC
 import sites_ref as S
@@ -32,6 +34,8 @@ LETTER_P = (.22, .22, .22, .22, .02, .02, .02, .02, .02, .01, .01)
 MAX_SAMPLES = 1_500_000
 MAX_ELEMENTS = 1 << 22
 HEADROOM = 0.8
+COLLAPSE_SHIFTS = (0, 0, 0, 0, 2, -3)                       # (mostly the aligner's own answer: the call conditions are about that one)
+CFG_BASE = 17000                                           # draw()'s second generator is default_rng(CFG_BASE + seed)
 
 
 def n_events(m, k, rna, prefix):
@@ -126,6 +130,10 @@ def draw(seed):
     shrink(lens, k, rna, prefix, dwell_mean, cfgs["chunk"])
     letters, p = (LETTERS + b"M", [v * 0.93 for v in LETTER_P] + [0.07]) if meth else (LETTERS, LETTER_P)
     batches = [[bytes(rng.choice(list(letters), m, p=p).astype(np.uint8)) for m in bt] for bt in lens]
+    # ---- the cfgs of the calls added since the table was drawn, from a generator of their own: every value above stays what it was
+    rng2 = np.random.default_rng(CFG_BASE + seed)
+    cfgs["call_observed"] = (CL.NEIGH_READ, int(rng2.choice(CS.TERM_CAPS)), int(rng2.choice(CS.LLR_MINS)), int(rng2.choice(CS.MIN_OBS)))
+    cfgs["collapse_shift"] = int(rng2.choice(COLLAPSE_SHIFTS))
     su = SC.Setup.of(f"drawn {seed}", prof, flags, k, seed, T, batches, amp_noise=amp, seed=int(rng.integers(1, 1 << 30)), **cfgs)
     su.drawn = dict(seed=seed, flag_set=f, shape=shape, dwell=(dwell_mean, dwell_std))
     return su
@@ -135,7 +143,7 @@ def describe(su):
     d = su.drawn
     return (f"seed {d['seed']}: flags {su.flags:#x} k {su.k} T {su.T} dwell {d['dwell'][0]}/{d['dwell'][1]} {d['shape']}, reads {[[len(r) for r in bt] for bt in su.batches]}, "
             f"chunk {su.chunk} {su.chunk_settings}, sites {su.site_geometries} focus {su.focus} ctx {su.site_ctx}, detect B {su.detect_b}, "
-            f"align {su.align_detected} / {su.align_truth}")
+            f"align {su.align_detected} / {su.align_truth}, call observed {su.call_observed}, collapse shift {su.collapse_shift}")
 
 
 def site_facts(su, reads):
@@ -162,6 +170,41 @@ def site_facts(su, reads):
     return cand, front, back, low, high
 
 
+def chain_facts(su, w, o=None):
+    """of one batch, from the chained references' groups w (Setup.expected) and the oracle's batch o: what the scale, collapse and call
+    groups hold of what can go wrong in them; w None: the figures of no batch.  Counts add up and flags are or-ed over a case's batches"""
+    out = dict(unseen_beside_summed=False, rd_dropped=0, fit_gain=False, fit_shift=False, fit_fallback=False, part_obs=0, no_obs=0, calls=set(), labels=set(),
+               call_outside=0, called=0, agree=0, site_steps=set(), two_in_kmer=False, site_first=False, site_last=False)
+    if w is None:
+        return out
+    co, ev_off = w["collapse pa 0"], w["collapse pa 0"]["off"]
+    for r in range(len(ev_off) - 1):
+        rows, ln = (co["rows"][key][ev_off[r]:ev_off[r + 1]] for key in ("ob_rows", "ob_len"))
+        out["unseen_beside_summed"] |= bool((ln == 0).any() and (rows >= 2).any())
+    out["rd_dropped"] = int(co["per_read"]["rd_dropped"].sum())
+    fit = w["scale fit"]["per_read"]
+    out["fit_gain"], out["fit_shift"] = bool((fit["gain"] != 65536).any()), bool((fit["shift"] != 0).any())
+    out["fit_fallback"] = bool((fit["n"] < 2).any())          # no row or one: no variance to fit a gain to
+    if not su.calls:
+        return out
+    k = su.k
+    c, t = w["call observed"], w["call true"]
+    lens = o["lens"][c["read"]]
+    p = c["rows"]["site_pos"].astype(np.int64)
+    span = np.minimum(p, lens - k) - np.maximum(0, p - k + 1) + 1
+    n_obs = c["rows"]["n_obs"]
+    out["part_obs"], out["no_obs"] = int(((n_obs > 0) & (n_obs < span)).sum()), int((n_obs == 0).sum())
+    out["calls"], out["labels"] = set(c["rows"]["call"].tolist()), set(c["rows"]["label"].tolist())
+    out["call_outside"], out["called"], out["agree"] = c["stat"][1:]
+    out["site_steps"] = set(o["step"][c["read"]].tolist())
+    a, kw = t["args"]
+    other = CL.vectorised(a[0], a[1], (CL.NEIGH_READ,) + CL.DEFAULT[1:], *a[3:], **kw)
+    out["two_in_kmer"] = bool((other["llr"] != t["rows"]["llr"]).any())
+    tp = t["rows"]["site_pos"]
+    out["site_first"], out["site_last"] = bool((tp == 0).any()), bool((tp == o["lens"][t["read"]] - 2).any())
+    return out
+
+
 def facts(su):
     """what the oracle and the references say of a case, the device nowhere: a dict of the figures test_fuzz_consumers.py's conditions are
     about.  Asserts the size conditions of the case"""
@@ -169,8 +212,8 @@ def facts(su):
     k, (L, St, W) = su.k, su.chunk
     out = dict(su.drawn, k=k, flags=su.flags, prefix=su.prefix, sites=su.sites, stride=(St > L) - (St < L), W=W, shapes=set(), samples=0,
                no_chunk_beside=False, label_over=False, label1=0, front=0, back=0, barren=False, ctx_low=0, ctx_high=0, long=0, masks=0, brief=False,
-               edge=False, more_rows=False, more_events=False, outside=0, steps=set(), shared=False)
-    keys = []
+               edge=False, more_rows=False, more_events=False, outside=0, steps=set(), shared=False, collapse_shift=su.collapse_shift, **chain_facts(su, None))
+    keys, site_keys = [], []
     for o in job:
         reads = o["reads"]
         short = [len(r["seq"]) < k for r in reads]
@@ -184,7 +227,12 @@ def facts(su):
         if len(reads) >= 2 and not all(short):
             out["shapes"] |= ({"short read first"} if short[0] else set()) | ({"short read last"} if short[-1] else set())
         seen = {}
-        w = su.expected(reads, seen=seen)
+        w = su.expected(reads, seen=seen, origin=(o["key0"], o["step"]))
+        for key, v in chain_facts(su, w, o).items():
+            out[key] = out[key] | v if isinstance(v, (bool, set)) else out[key] + v
+        if su.calls:
+            sk, (lo, hi) = w["call observed"]["rows"]["site_key"], su.window()      # (a read without a step has INT64_MIN there: below the window)
+            site_keys.append(set(sk[(sk >= lo) & (sk < hi)].tolist()))
         for name, g in w.items():                           # the element bound, of the outputs the references hold
             if name.split()[0] in ("chunks", "targets", "sites"):
                 el = sum(a.size for a in g["rows"].values()) + len(g["read"])
@@ -212,6 +260,7 @@ def facts(su):
         keys.append(set(su.keys(o, np.arange(len(reads))).tolist()))
     assert out["samples"] <= MAX_SAMPLES, f"{describe(su)}: {out['samples']} samples"
     out["shared"] = any(keys[a] & keys[b] for a in range(len(keys)) for b in range(a + 1, len(keys)))
+    out["site_shared"] = any(site_keys[a] & site_keys[b] for a in range(len(site_keys)) for b in range(a + 1, len(site_keys)))
     for c, (kw, norm, trim) in su.pile_cfgs().items():
         out["outside"] += su.expected_pileup(kw, norm, trim)[2]
     return out

@@ -6,13 +6,16 @@ import numpy as np
 import torch  # noqa: F401  (before the library is loaded: the HIP runtime torch brings is the one the library then uses)
 
 import align_ref as AL
+import call_ref as CL
 import chunks_ref as R
+import collapse_ref as CO
 import detect_ref as DT
 import detect_vec as DVEC
 import events_ref as EV
 import events_vec as VEC
 import orc
 import pileup_ref as PR
+import scale_ref as SCL
 import segments_ref as SR
 import sites_ref as S
 import targets_ref as T
@@ -29,6 +32,10 @@ DETECT_B = (3, 6, 4.0, 3.0, 0.2)                            # "detect B": thresh
 ALIGN_TRUTH = (256, 1024, 16384)                            # "align truth": the cfg of tests/test_align.py
 ALIGN_DEFAULT = (4096, 4096, 65536)                         # SQG_ALIGN_DEFAULT, typed out: "align detected" passes no cfg
 EVENT_INDICES = ("true_ev", "al_ev")                        # the columns that hold batch-wide event indices: restrict() renumbers them
+# (of the scale, collapse and call groups only "align scaled" has such a column, al_ev: the collapse groups' rows ARE the events, in the
+# rank's own order; site_pos counts bases within the read and site_key is absolute: neither is renumbered)
+CALL_OBSERVED = (CL.NEIGH_READ, 256 * 50, 0, 2)             # "call observed": (neigh, term_cap, llr_min, min_obs)
+CALL_ROWS = tuple(n for n in CL.OUTPUTS if n != "site_read")
 KEY_BASE = (1 << 40) + 12345                                # the caller's origin of the staged jobs: keys past 32 bits
 METH_LETTERS = b"ACGTM" + b"ACGTM" + b"ACGTM" + b"mN"
 
@@ -71,6 +78,11 @@ CFGS = dict(
     align_rows=("detect A",),                               # the detectors whose rows are aligned: "align detected", "align detected B"
     align_truth=ALIGN_TRUTH,
     pile_kmer=False,                                        # True: pile_cfgs has a by="kmer" pileup without a prefix too
+    call_observed=CALL_OBSERVED,                            # "align scaled" takes the cfg of align_detected; "call true" the binding's defaults
+    # added to "align scaled"'s al_ev before collapse and pileup_rows take it.  The banded aligner assigns every row to an event of its
+    # own read, so under 0 no row is ever dropped; under another value the rows at one end of a read point past it -- into the
+    # neighbouring read's events or past the batch's -- and are (sqg_collapse.h: not an event of the row's own read)
+    collapse_shift=0,
 )
 
 
@@ -104,9 +116,12 @@ class Setup:
         self.sampled = j["kind"] in ("range_sampled", "worker_sampled")
         self.by_worker = j["kind"] in ("worker_staged", "worker_sampled")
         self.sites = not self.rna and not self.prefix
+        self.calls = self.meth and self.sites               # the contexts include/sqg_call.h takes; the others are refused under ...
+        self.call_flag = "SQG_RNA" if self.rna else "SQG_PREFIX" if self.prefix else "SQG_METH"       # ... this flag's name
         self.n_rows = self.T * len(self.mean)
         self.contigs = self.names = None
         self.batches, self.amp_noise, self.seed = None, 1.0, SEED
+        self._chains = {}                                   # id of a job's batch's reads -> job_chain()'s entry
         assert set(cfgs) <= set(CFGS), sorted(set(cfgs) - set(CFGS))
         for key, default in CFGS.items():
             setattr(self, key, cfgs.get(key, default))
@@ -223,7 +238,7 @@ class Setup:
         names = {"detect A": "align detected", "detect B": "align detected B"}
         return {d: (names[d], cfg, ALIGN_DEFAULT if cfg is None else cfg) for d in self.detect_settings(threaded) if d in self.align_rows}
 
-    def expected_detect_align(self, reads, ev, threaded=False, seen=None, plain=False):
+    def expected_detect_align(self, reads, ev, threaded=False, seen=None, plain=False, align=True):
         """the groups of sqg_batch_detect and sqg_batch_align: detect_ref and align_ref over the reads and over ev, events_ref's table of
         them ("pa", untrimmed).  seen: a dict that gets detect_ref's info of every detect group.  The two references walk every row in
         Python, some seconds for a job's rows, so what walks here is their second statement each -- detect_vec.batch_rows_of_reads (the
@@ -240,6 +255,8 @@ class Setup:
                 seen[name] = info
             out[name] = dict(off=w["det_off"], read=w["dt_read"], rows={key: w[key] for key in DT.PER_ROW if key != "dt_read"},
                              per_read=dict(med2=w["med2"], mad4=w["mad4"]))
+        if not align:                                       # (the detect groups alone: what job_chain() starts from)
+            return out
         ev_off = ev["ev_off"]
         for d, (name, _, cfg) in self.align_settings(threaded).items():
             w = det[d]
@@ -258,12 +275,116 @@ class Setup:
         return out
 
     # ---- the references, as groups: name -> dict(off [n_reads + 1], read [rows], rows {key: [rows, ...]}, per_read {key: [n_reads]})
-    def expected(self, reads, threaded=False, seen=None):
-        """seen: as in expected_detect_align"""
+    def collapse_settings(self, threaded=False):
+        """(norm, trim) of the "collapse" groups"""
+        return [("pa", False)] + ([] if threaded else [("medmad", self.prefix)])
+
+    def event_table(self, reads, norm, trim, tables=None):
+        """events_ref's table of the reads under (norm, trim); tables: those at hand, {(norm, trim): table}, added to"""
+        key = (norm, bool(trim))
+        if tables is None or key not in tables:
+            p = self.prof
+            w = EV.batch_events(reads, self.mean, self.k, self.rna, self.meth, self.prefix, self.sps, norm, trim, p.range, p.digitisation)
+            if tables is None:
+                return w
+            tables[key] = w
+        return tables[key]
+
+    def collapse_of(self, reads, inner, norm, trim, tables=None):
+        """collapse_ref over the rows the "collapse" groups take -- detect A's, assigned by "align scaled"'s al_ev --, the reads'
+        constants from events_ref's table under (norm, trim)"""
+        p = self.prof
+        if norm == "pa":
+            consts = dict(offset=[r["offset"] for r in reads], rng=p.range, dig=p.digitisation)
+        elif (tables is None or (norm, bool(trim)) not in tables) and not trim and not self.prefix:
+            st = [R.stats(np.asarray(r["sig"], np.int16)) for r in reads]       # (the whole read's statistics: what pileup_table takes too)
+            consts = dict(med2=np.array([s[0] for s in st], np.int32), mad4=np.array([s[1] for s in st], np.int32))
+        else:
+            t = self.event_table(reads, norm, trim, tables)
+            consts = dict(med2=t["med2"], mad4=t["mad4"])
+        d = inner["det"]
+        return CO.collapse(d["off"], inner["rows_ev"], d["rows"]["sum"], d["rows"]["sumsq"], d["rows"]["dt_len"], inner["ev_off"], norm, **consts)
+
+    def expected_chain(self, reads, groups, tables, origin=None, threaded=False):
+        """the groups of sqg_batch_scale, sqg_batch_align_scaled, sqg_batch_collapse and sqg_batch_call, chained reference to reference
+        from the oracle's reads: detect A's rows (groups["detect A"]) -> scale_ref (moments) -> the scaled aligner -> scale_ref (fit) and
+        collapse_ref -> call_ref on the collapsed rows under the fitted scaling; and call_ref on the true table.  tables: events_ref's,
+        {(norm, trim): table}, ("pa", False) among them.  origin: (key0, step) of the reads; without one the call groups have no
+        site_key.  -> (the groups, what expected_pileup_rows and the cases' facts take of the chain).  A call group has "stat" as well,
+        "call observed" under the job's window, and "freq": what it adds to the context's frequency table"""
+        p, k = self.prof, self.k
+        ev = tables[("pa", False)]
+        ev_off = ev["ev_off"]
+        d = groups["detect A"]
+        off, read, s1, ln = d["off"], d["read"], d["rows"]["sum"], d["rows"]["dt_len"]
+        cfg = ALIGN_DEFAULT if self.align_detected is None else self.align_detected
+        out = {}
+        mom = SCL.vectorised(off, s1, ln, ev_off, ev["level_raw"], SCL.MOMENTS)
+        out["scale moments"] = dict(off=off, read=read, rows={}, per_read=mom)
+        a = SCL.align_scaled(off, s1, ln, ev_off, ev["level_raw"], self.rna, cfg, mom["gain"], mom["shift"], one=orc.align_banded)
+        out["align scaled"] = dict(off=off, read=read, rows=dict(al_ev=a["al_ev"]), per_read=dict(al_cost=a["al_cost"], al_edge=a["al_edge"]))
+        fit = SCL.vectorised(off, s1, ln, ev_off, ev["level_raw"], SCL.FIT, ev=a["al_ev"])
+        out["scale fit"] = dict(off=off, read=read, rows={}, per_read=fit)
+        inner = dict(det=d, rows_ev=a["al_ev"] + self.collapse_shift, ev_off=ev_off, ev=ev, mom=mom, fit=fit, ob={})
+        for norm, trim in self.collapse_settings(threaded):
+            ob = inner["ob"][(norm, bool(trim))] = self.collapse_of(reads, inner, norm, trim, tables)
+            out[f"collapse {norm} {int(trim)}"] = dict(off=ev_off, read=ev["ev_read"], rows={key: ob[key] for key in CO.OUTPUTS if key != "rd_dropped"},
+                                                      per_read=dict(rd_dropped=ob["rd_dropped"]))
+        if self.calls:
+            ob = inner["ob"][("pa", False)]
+            model_ = CL.call_model(self.stdv, p.range, p.digitisation)
+            args = lambda cfg, s, n: ([r["seq"] for r in reads], k, cfg, s, n, ev_off, np.asarray(self.mean, np.float32), [r["offset"] for r in reads],      # noqa: E731
+                                      p.range, p.digitisation, *model_)
+            inner["call true args"] = (args(CL.DEFAULT, ev["sum"], ev["ev_len"]), dict(origin=origin))
+            inner["call observed args"] = (args(self.call_observed, ob["ob_sum"], ob["ob_len"]),
+                                           dict(scale=(fit["gain"], fit["shift"]), origin=origin, window=self.window() if origin is not None else None))
+            for name in ("call true", "call observed"):
+                w = inner[name] = CL.vectorised(*inner[f"{name} args"][0], **inner[f"{name} args"][1])
+                out[name] = dict(off=w["site_off"], read=w["site_read"], rows={key: w[key] for key in CALL_ROWS if key in w}, per_read={}, stat=w["stat"], freq=w.get("freq"),
+                                 args=inner[f"{name} args"])
+        return out, inner
+
+    def job_chain(self):
+        """per batch of the oracle's job: (the chain's groups, its inner values, the event tables) of the whole batch"""
+        out = []
+        for o in self.oracle_job():
+            if id(o["reads"]) not in self._chains:          # (expected() of the whole batch under the job's own origin leaves it there)
+                tables = {}
+                ev = self.event_table(o["reads"], "pa", False, tables)
+                groups, inner = self.expected_chain(o["reads"], self.expected_detect_align(o["reads"], ev, threaded=True, align=False), tables, (o["key0"], o["step"]))
+                self._chains[id(o["reads"])] = (groups, inner, tables)
+            out.append(self._chains[id(o["reads"])])
+        return out
+
+    def expected_pileup_rows(self, kw, norm, trim):
+        """collapse_ref.pileup_rows over the whole job, batch after batch into the same sums -> (the six arrays, the four statistics)"""
+        by = PR.BY_KMER if kw["by"] == "kmer" else PR.BY_REF
+        split = sum({"strand": PR.SPLIT_STRAND, "meth": PR.SPLIT_METH}[s] for s in kw.get("split", ()))
+        segs = sum(1 << q for q in kw.get("segs", ()))
+        lo, hi = (kw["lo"], kw["hi"]) if by == PR.BY_REF else (0, len(self.mean))
+        into, stats = None, [0, 0, 0, 0]
+        for o, (_, inner, tables) in zip(self.oracle_job(), self.job_chain()):
+            ob = self.collapse_of(o["reads"], inner, norm, trim, tables)
+            ev = tables[("pa", False)]                      # (ev_read, kmer and seg are the same under every norm and trim)
+            into, *st = CO.pileup_rows(ob, ev, inner["ev_off"], o["key0"], o["step"], o["lens"], self.k, self.rna, self.prefix, by, split, segs, lo, hi, into)
+            stats = [a + b for a, b in zip(stats, st)]
+        return into, tuple(stats)
+
+    def expected_call_freq(self):
+        """what "call observed" adds to a frequency table over window() in the whole job: the reference's freq, summed"""
+        lo, hi = self.window()
+        total = {n: np.zeros(hi - lo, np.uint32) for n in CL.FREQ}
+        for _, inner, _ in self.job_chain():
+            for n in CL.FREQ:
+                total[n] += inner["call observed"]["freq"][n]
+        return total
+
+    def expected(self, reads, threaded=False, seen=None, origin=None):
+        """seen: as in expected_detect_align; origin: as in expected_chain"""
         p, k, rna, meth, prefix, sps, mean = self.prof, self.k, self.rna, self.meth, self.prefix, self.sps, self.mean
         L, St, W = self.chunk
         n = len(reads)
-        out = {}
+        out, tables = {}, {}
         for dtype, norm in self.chunk_settings[:1] if threaded else self.chunk_settings:
             fdt = np.float16 if dtype == "f16" else np.float32
             if n == 0:
@@ -287,11 +408,15 @@ class Setup:
                 out[f"sites {Lw}"] = dict(off=w["site_off"], read=w["site_read"], rows={key: w[key] for key in S.KEYS if key != "site_read"},
                                           per_read=dict(med2=w["med2"], mad4=w["mad4"]))
         for norm, trim in self.event_settings[:1] if threaded else self.event_settings:
-            w = EV.batch_events(reads, mean, k, rna, meth, prefix, sps, norm, trim, p.range, p.digitisation)
+            w = self.event_table(reads, norm, trim, tables)
             out[f"events {norm} {int(trim)}"] = dict(off=w["ev_off"], read=w["ev_read"], rows={key: w[key] for key in EV.PER_EVENT if key != "ev_read"},
                                                     per_read=dict(med2=w["med2"], mad4=w["mad4"]))
             if (norm, trim) == tuple(self.event_settings[0]):
                 out.update(self.expected_detect_align(reads, w, threaded, seen))
+        groups, inner = self.expected_chain(reads, out, tables, origin, threaded)
+        if not threaded and origin is not None and any(reads is o["reads"] and origin[0] is o["key0"] and origin[1] is o["step"] for o in self.oracle_job()):
+            self._chains[id(reads)] = (groups, inner, tables)   # a whole batch of the job under the job's origin: what job_chain() takes
+        out.update(groups)
         if prefix and not threaded:
             seg, shift = SR.batch_segments(reads, k, rna, prefix, sps)
             out["segments"] = dict(off=np.arange(n + 1, dtype=np.int64), read=np.arange(n, dtype=np.int32), rows=dict(seg=seg, shift=shift), per_read={})
@@ -331,29 +456,40 @@ class Setup:
         return into, counted, outside
 
     # ---- the consumer calls of a batch, as the same groups
-    def consume(self, b, threaded=False, order=None, extra=()):
-        """extra: further steps (callables that take the dict of groups), behind the listed ones.  order: a permutation of
-        range(len(self.consume_steps(b, threaded)) + len(extra)) -- the steps run in that order instead of the listed one.
-        The aligner takes a detector's own tensors: if its step comes first, the detector's step runs there, in front of it, and not
-        again.  What is returned does not depend on the order"""
-        steps = self.consume_steps(b, threaded) + [(None, step) for step in extra]
+    def consume(self, b, threaded=False, order=None, extra=(), origin=None, freq=None, want=None, kept=None):
+        """extra: further steps (callables that take the dict of groups), behind the listed ones; one given as (label, step) runs behind
+        the listed step of that label (a group's name).  order: a permutation of range(len(self.consume_steps(b, threaded)) + len(extra))
+        -- the steps run in that order instead of the listed one.  A call that takes another call's tensors as they are -- the aligner
+        the detector's, the collapse the scaled aligner's, the caller the collapse's and the fit's -- names the steps that must have run:
+        if its step comes first, those run there, in front of it, and not again.  What is returned does not depend on the order.
+        origin, freq, want, kept: as in consume_steps"""
+        steps = self.consume_steps(b, threaded, origin, freq, want, kept)
+        at = {step.label: i for i, (_, step) in enumerate(steps)}
+        steps += [((at[step[0]],), step[1]) if isinstance(step, tuple) else (None, step) for step in extra]
         out, ran = {}, set()
+
+        def run(i):
+            if i in ran:
+                return
+            ran.add(i)
+            need = steps[i][0]
+            for j in () if need is None else (need,) if isinstance(need, int) else need:
+                run(j)
+            steps[i][1](out)
         for i in range(len(steps)) if order is None else order:
-            need, step = steps[i]
-            for j in ([] if need is None else [need]) + [i]:
-                if j not in ran:
-                    ran.add(j)
-                    steps[j][1](out)
+            run(int(i))
         assert len(ran) == len(steps)
         return out
 
-    def consume_steps(self, b, threaded=False):
-        """the calls of consume() on batch b in the listed order: [(the index of the step that must have run before, or None, the step)];
-        a step takes the dict of groups and adds its own"""
+    def consume_steps(self, b, threaded=False, origin=None, freq=None, want=None, kept=None):
+        """the calls of consume() on batch b in the listed order: [(the steps that must have run before -- None, an index or a tuple of
+        them --, the step)]; a step takes the dict of groups and adds its own, and has its group's name as .label.  origin: what
+        Batch.call takes as origin= (Setup.origin); freq: the CallFreq "call observed" adds to; want: the expected groups -- the call
+        steps assert their stat against them; kept: a dict that gets the tensors the steps hand on ("rows": what collapse takes)"""
         L, St, W = self.chunk
         trim = self.prefix
         cpu = _host
-        steps, kept = [], {}
+        steps, kept = [], {} if kept is None else kept
 
         def chunks(dtype, norm):
             def step(out):
@@ -412,22 +548,90 @@ class Setup:
             seg, shift = b.segments()
             out["segments"] = dict(off=np.arange(b.n_reads + 1, dtype=np.int64), read=np.arange(b.n_reads, dtype=np.int32), rows=dict(seg=cpu(seg), shift=cpu(shift)), per_read={})
 
+        def scale(name, mode):                              # detect A's rows; mode "fit": assigned by "align scaled"'s al_ev
+            def step(out):
+                dt = kept["detect A"]
+                sc = kept[name] = b.scale(dt.det_off, dt.sum, dt.dt_len, ev=kept["align scaled"].al_ev if mode == "fit" else None, mode=mode)
+                assert sc.n_rows == dt.n_rows
+                out[name] = dict(off=sc.row_off, read=cpu(dt.dt_read), rows={}, per_read={key: cpu(getattr(sc, key)) for key in SCL.OUTPUTS})
+            return step
+
+        def align_scaled(out):                              # under the moments estimate and the cfg of "align detected"
+            dt, sc, cfg = kept["detect A"], kept["scale moments"], self.align_detected
+            al = kept["align scaled"] = b.align(dt.det_off, dt.sum, dt.dt_len, scale=(sc.gain, sc.shift)) if cfg is None else b.align(dt.det_off, dt.sum, dt.dt_len, cfg, scale=(sc.gain, sc.shift))
+            assert al.n_rows == dt.n_rows
+            kept["rows"] = (dt.det_off, al.al_ev + self.collapse_shift if self.collapse_shift else al.al_ev, dt.sum, dt.sumsq, dt.dt_len)
+            out["align scaled"] = dict(off=al.row_off, read=cpu(dt.dt_read), rows=dict(al_ev=cpu(al.al_ev)), per_read=dict(al_cost=cpu(al.al_cost), al_edge=cpu(al.al_edge)))
+
+        def collapse(name, norm, tr):
+            def step(out):
+                co = kept[name] = b.collapse(*kept["rows"], norm=norm, trim=tr)
+                ev = b.events(outputs=("ev_read",))
+                assert co.n_events == b.n_events and co.n_rows == kept["detect A"].n_rows
+                out[name] = dict(off=b.ev_off, read=cpu(ev.ev_read), rows={key: cpu(getattr(co, key), key) for key in CO.OUTPUTS if key != "rd_dropped"},
+                                 per_read=dict(rd_dropped=cpu(co.rd_dropped)))
+            return step
+
+        def call(name, rows, scaled=False, **kw):
+            def step(out):
+                scale_ = (kept["scale fit"].gain, kept["scale fit"].shift) if scaled else None
+                ch = b.call(*rows(), scale=scale_, origin=origin, **kw)
+                plan, ns = b.call_plan()
+                assert ns == ch.n_sites == ch.stat[0] == len(ch.site_read) and plan[-1] == ns
+                if want is not None:                        # (without a frequency table the call counts nothing as outside)
+                    ws = want[name]["stat"]
+                    assert ch.stat == (ws if kw.get("freq") is not None else (ws[0], 0) + ws[2:]), f"{name}: stat {ch.stat}, expected {ws}"
+                out[name] = dict(off=ch.site_off, plan=plan, read=cpu(ch.site_read), rows={key: cpu(getattr(ch, key)) for key in CALL_ROWS if getattr(ch, key) is not None},
+                                 per_read={})
+            return step
+
+        def call_true():
+            ev = b.events(outputs=("sum", "ev_len"))
+            return ev.sum, ev.ev_len
+
+        def call_observed():                                # the collapsed rows: int64 lengths, events without a row among them
+            return kept["collapse pa 0"].ob_sum, kept["collapse pa 0"].ob_len
+
+        def call_refused(out):
+            try:
+                b.call_plan()
+            except api.SqgError as e:
+                assert e.code == -1 and self.call_flag in str(e), str(e)
+            else:
+                raise AssertionError(f"sqg_call_plan did not refuse a context with {self.call_flag}")
+
+        def add(need, step, label):
+            step.label = label
+            steps.append((need, step))
+            return len(steps) - 1
+
         for dtype, norm in self.chunk_settings[:1] if threaded else self.chunk_settings:
-            steps.append((None, chunks(dtype, norm)))
+            add(None, chunks(dtype, norm), f"chunks {dtype} {norm}")
         if self.sites:
             for Lw, before in self.site_geometries[:1] if threaded else self.site_geometries:
-                steps.append((None, sites(Lw, before)))
+                add(None, sites(Lw, before), f"sites {Lw}")
         for norm, tr in self.event_settings[:1] if threaded else self.event_settings:
-            steps.append((None, events(norm, tr)))
+            add(None, events(norm, tr), f"events {norm} {int(tr)}")
         aligned = self.align_settings(threaded)
         for name, (_, cfg, norm, tr) in self.detect_settings(threaded).items():
-            steps.append((None, detect(name, cfg, norm, tr)))
+            at = add(None, detect(name, cfg, norm, tr), name)
             if name in aligned:
-                steps.append((len(steps) - 1, align_detected(name, aligned[name][0], aligned[name][1])))
+                add(at, align_detected(name, aligned[name][0], aligned[name][1]), aligned[name][0])
+            if name == "detect A":                          # the chain: every call takes the tensors of the ones before it as they are
+                mom = add(at, scale("scale moments", "moments"), "scale moments")
+                als = add(mom, align_scaled, "align scaled")
+                fit = add(als, scale("scale fit", "fit"), "scale fit")
+                cos = [add(als, collapse(f"collapse {norm} {int(tr)}", norm, tr), f"collapse {norm} {int(tr)}") for norm, tr in self.collapse_settings(threaded)]
         if not threaded:
-            steps.append((None, align_truth))
+            add(None, align_truth, "align truth")
         if self.prefix and not threaded:
-            steps.append((None, segments))
+            add(None, segments, "segments")
+        if self.calls:
+            add(None, call("call true", call_true), "call true")
+            neigh, term_cap, llr_min, min_obs = self.call_observed
+            add((cos[0], fit), call("call observed", call_observed, scaled=True, freq=freq, neigh=neigh, term_cap=term_cap, llr_min=llr_min, min_obs=min_obs), "call observed")
+        else:
+            add(None, call_refused, "call refused")
         return steps
 
     def origin(self, o, idx):
@@ -449,9 +653,9 @@ def stored_order(ev_off, rna):
 
 
 def _host(t, key=None):
-    """a tensor on the host; the k-mer columns as the uint32 they are"""
+    """a tensor on the host; the k-mer columns and collapse's row counts as the uint32 they are"""
     a = t.cpu().numpy()
-    return a.view(np.uint32) if key == "kmer" else a
+    return a.view(np.uint32) if key in ("kmer", "ob_rows") else a
 
 
 def assert_groups(got, want, what):
@@ -496,6 +700,11 @@ def restrict(groups, idx):
 def pile_arrays(p):
     """the six arrays of a Pileup on the host (n as the uint32 it is)"""
     return {n: (lambda a: a.view(np.uint32) if n == "n" else a)(getattr(p, n).cpu().numpy()) for n in api.PILEUP_OUTPUTS}
+
+
+def freq_arrays(f):
+    """the four arrays of a CallFreq on the host, as the uint32 they are"""
+    return {n: getattr(f, n).cpu().numpy().view(np.uint32) for n in api.CALL_FREQ}
 
 
 # ---------------------------------------------------------------------------------------------------------- drivers (GPU)

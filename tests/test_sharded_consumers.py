@@ -1,5 +1,6 @@
 """The consumer calls -- sqg_batch_chunks / sqg_chunk_plan, sqg_batch_chunk_targets, sqg_batch_segments and the *_trimmed calls,
-sqg_site_plan / sqg_batch_sites, sqg_batch_events, sqg_batch_pileup, sqg_detect_plan / sqg_batch_detect, sqg_batch_align -- on batches
+sqg_site_plan / sqg_batch_sites, sqg_batch_events, sqg_batch_pileup, sqg_detect_plan / sqg_batch_detect, sqg_batch_align, sqg_batch_scale,
+sqg_batch_align_scaled, sqg_batch_collapse, sqg_batch_pileup_rows, sqg_call_plan / sqg_batch_call -- on batches
 made the way several GPUs make them: range-sharded contexts (sqg_batch_run_begin / _end), worker-sharded contexts, and contexts on host
 threads of their own (tests/shard_cases.py has the jobs and the drivers).  What a rank that holds reads idx of the job must produce is
 the numpy reference of the call's header over [reads[i] for i in idx], the reads being those of the oracle's single-process run of the
@@ -56,6 +57,49 @@ def _detect_align_hold(su, reads, what):
     return rows
 
 
+def _chain_holds(su, job):
+    """what the scale, collapse and call groups need of a job, asserted of the chained references over the whole job (Setup.job_chain):
+    in every rank that holds a read the fit gives a gain other than 65536 and a shift other than 0, an event has no row and another
+    one two or more (the reads shorter than a k-mer of the staged range jobs, the first or last of their ranks, are among the reads
+    scaled: test_the_jobs_hold_what_can_go_wrong asserts where they lie); and under SQG_METH every rank that holds a read holds a CpG
+    site, the site counts differ from rank to rank, a staged job has sites that the frequency table does not take (reads without a
+    step), all three call values occur, and a frequency key is added to by sites of two different ranks"""
+    name = su.name
+    chain = su.job_chain()
+    lo, hi = su.window()
+    rank_keys = [set() for _ in range(su.G)]
+    calls, outside = set(), 0
+    for bi, (o, (groups, inner, _)) in enumerate(zip(job, chain)):
+        n = len(o["reads"])
+        fit, co = groups["scale fit"]["per_read"], groups["collapse pa 0"]
+        ev_off = co["off"]
+        sites = []
+        for g in range(su.G):
+            idx = su.rank_reads(n, g)
+            if not len(idx):
+                continue
+            ev = np.concatenate([np.arange(ev_off[i], ev_off[i + 1]) for i in idx])
+            row = dict(gains=int((fit["gain"][idx] != 65536).sum()), shifts=int((fit["shift"][idx] != 0).sum()), fallbacks=int((fit["n"][idx] < 2).sum()),
+                       unseen=int((co["rows"]["ob_rows"][ev] == 0).sum()), summed=int((co["rows"]["ob_rows"][ev] >= 2).sum()), dropped=int(co["per_read"]["rd_dropped"][idx].sum()))
+            assert row["gains"] and row["shifts"] and row["unseen"] and row["summed"], f"{name} batch {bi} rank {g}: {row}"
+            if su.calls:
+                c = groups["call observed"]
+                mine = np.isin(c["read"], idx)
+                key = c["rows"]["site_key"][mine]
+                row.update(sites=int(mine.sum()), unobserved=int((c["rows"]["n_obs"][mine] == 0).sum()), called=int((c["rows"]["call"][mine] != 0).sum()))
+                rank_keys[g] |= set(key[(key >= lo) & (key < hi)].tolist())
+                calls |= set(c["rows"]["call"][mine].tolist())
+                sites.append(row["sites"])
+            print(f"{name} batch {bi} rank {g}: " + ", ".join(f"{v} {key}" for key, v in row.items()))
+        if su.calls:
+            outside += groups["call observed"]["stat"][1]
+            assert min(sites) > 0 and len(set(sites)) == len(sites), f"{name} batch {bi}: call sites per rank {sites}"
+    if su.calls:
+        both = set().union(*[rank_keys[a] & rank_keys[b] for a in range(su.G) for b in range(a + 1, su.G)])
+        print(f"{name}: {len(both)} frequency keys added to by sites of two different ranks, {outside} sites outside, call values {sorted(calls)}")
+        assert both and calls == {0, 1, 2} and (outside > 0 or su.sampled)
+
+
 @pytest.mark.parametrize("name", SHARDED)
 def test_the_jobs_hold_what_can_go_wrong(name):
     """from the oracle and the numpy references alone: every rank but the designated empty one holds a read; a sampled DNA job holds both
@@ -63,7 +107,7 @@ def test_the_jobs_hold_what_can_go_wrong(name):
     piled up by position has a key that reads of two different ranks add to; a staged job's steps take all three values in every rank;
     every rank of the staged range jobs holds a read shorter than a k-mer, as its first or last read among others; the chunk, site,
     event and detected-row counts of a batch's ranks are above zero and differ from rank to rank; and every rank that holds a read holds
-    what the detect and align groups need (_detect_align_hold)"""
+    what the detect and align groups need (_detect_align_hold) and what the scale, collapse and call groups need (_chain_holds)"""
     su = SC.Setup(name)
     j = su.job
     job = su.oracle_job()
@@ -122,6 +166,7 @@ def test_the_jobs_hold_what_can_go_wrong(name):
     if su.sites:
         assert dropped > 0 and labels == ({0, 1} if su.meth else {0})
     assert shared_job > 0
+    _chain_holds(su, job)
     kw = su.pile_cfgs()["ref_window"][0]
     allk = np.concatenate([su.keys(o, np.arange(len(o["reads"]))) for o in job])
     assert kw["lo"] < kw["hi"] and (allk < kw["lo"]).any() and (allk >= kw["hi"]).any()          # the window cuts reads
@@ -192,15 +237,38 @@ def _assert_pile(got, want, what):
 @pytest.mark.parametrize("name,mode", RUNS, ids=RUN_IDS)
 def test_consumers_on_every_rank(name, mode):
     """every output of every consumer call on every rank's batch against the reference of that rank's reads, and against the plain single
-    context's rows of those reads; the rank with the empty range makes every call succeed with zero rows"""
+    context's rows of those reads; the rank with the empty range makes every call succeed with zero rows.  The accumulating calls of
+    the chain -- sqg_batch_pileup_rows over the rows the collapse steps take, under every cfg of pile_cfgs, and the frequency table
+    "call observed" adds to (a sampled rank under the NULL origin: the keys from its own range of the sampler's records) -- go into
+    objects of the rank's own: their sums over the ranks, the single context's and the references' over the whole job are the same
+    bytes, and so are the statistics"""
     su = SC.Setup(name)
     job = su.oracle_job()
-    got = {}
+    cfgs = su.pile_cfgs()
+    new = lambda gen, c: gen.new_pileup(norm=cfgs[c][1], trim=cfgs[c][2], **cfgs[c][0])      # noqa: E731
+    window = su.window()
+
+    def consume(b, bi, idx, piles, stats, freq, want=None):
+        """every group of the batch; the rows' pileups into piles / stats (c -> the Pileup, the four statistics), the calls into freq"""
+        kept, o = {}, job[bi]
+        origin = su.origin(o, idx)
+
+        def pile_rows(c):
+            def step(out):
+                st = b.pileup_rows(piles[c], *kept["rows"], origin=origin if cfgs[c][0]["by"] == "ref" else None)
+                stats[c] = [a + v for a, v in zip(stats[c], st)]
+            return "align scaled", step
+        return su.consume(b, extra=[pile_rows(c) for c in cfgs], origin=origin, freq=freq, want=want, kept=kept)
+
+    got, piles, stats, freqs = {}, {}, {}, {}
     for bi, g, b, idx in SC.DRIVERS[su.job["kind"]](su, mode):
         reads = [job[bi]["reads"][i] for i in idx]
         assert b.n_reads == len(idx)
-        out = su.consume(b)
-        SC.assert_groups(out, su.expected(reads), f"{name} batch {bi} rank {g}")
+        if g not in piles:
+            piles[g], stats[g], freqs[g] = {c: new(b.gen, c) for c in cfgs}, {c: [0, 0, 0, 0] for c in cfgs}, b.gen.new_call_freq(*window) if su.calls else None
+        want = su.expected(reads, origin=(job[bi]["key0"][idx], job[bi]["step"][idx]))
+        out = consume(b, bi, idx, piles[g], stats[g], freqs[g], want)
+        SC.assert_groups(out, want, f"{name} batch {bi} rank {g}")
         if len(idx) == 0:
             assert (bi, g) in su.job.get("empty", ())
             for gname, grp in out.items():
@@ -218,10 +286,28 @@ def test_consumers_on_every_rank(name, mode):
                 assert all((a == 7).all() for a in SC.pile_arrays(p).values()), "an empty range touched the pileup"
         got[(bi, g)] = out
     assert len(got) == su.G * len(job)
+    one = None
     for bi, b in SC.single(su, mode):
-        whole = su.consume(b)
+        one = one or ({c: new(b.gen, c) for c in cfgs}, {c: [0, 0, 0, 0] for c in cfgs}, b.gen.new_call_freq(*window) if su.calls else None)
+        whole = consume(b, bi, np.arange(b.n_reads), *one)
         for g in range(su.G):
             SC.assert_groups(got[(bi, g)], SC.restrict(whole, su.rank_reads(b.n_reads, g)), f"{name} batch {bi} rank {g} against the single context")
+    for c, (kw, norm, trim) in cfgs.items():
+        want, st = su.expected_pileup_rows(kw, norm, trim)
+        print(f"{name} {c}: rows piled up: (counted, outside, unseen, dropped) {st}, most reads on one key {int(want['n'].max())}")
+        assert st[0] > 0 and st[2] > 0 and int(want["n"].max()) >= 2
+        _assert_pile(_pile_sum([SC.pile_arrays(piles[g][c]) for g in range(su.G)]), want, f"{name} {c}: the sum of the ranks' pileups of rows")
+        _assert_pile(SC.pile_arrays(one[0][c]), want, f"{name} {c}: the single context's pileup of rows")
+        assert tuple(sum(stats[g][c][i] for g in range(su.G)) for i in range(4)) == tuple(one[1][c]) == st, f"{name} {c}: the statistics of the rows piled up"
+    if su.calls:
+        want = su.expected_call_freq()
+        ranks = [SC.freq_arrays(freqs[g]) for g in range(su.G)]
+        print(f"{name}: call frequency: {int(want['cov'].sum())} sites on {int((want['cov'] > 0).sum())} keys, most on one key {int(want['cov'].max())}, {int(want['called'].sum())} called, "
+              f"{int(want['meth'].sum())} as methylated; per rank {[int(r['cov'].sum()) for r in ranks]}")
+        assert int(want["cov"].max()) >= 2 and min(int(r["cov"].sum()) for r in ranks) > 0
+        for n in api.CALL_FREQ:
+            np.testing.assert_array_equal(sum(r[n] for r in ranks), want[n], err_msg=f"{name}: the sum of the ranks' call frequencies: {n}")
+            np.testing.assert_array_equal(SC.freq_arrays(one[2])[n], want[n], err_msg=f"{name}: the single context's call frequency: {n}")
 
 
 @pytest.mark.gpu
@@ -358,19 +444,23 @@ def test_lifetime_of_a_batch_in_range_mode():
     su = SC.Setup("lifetime_g1")
     rk = SC.RangeRanks(su)
     try:
-        _lifetime(su, rk, su.staged_reads(), [o["reads"] for o in su.oracle_job()])
+        _lifetime(su, rk, su.staged_reads(), su.oracle_job())
     finally:
         rk.close()
 
 
-def _lifetime(su, rk, bts, reads):
+def _lifetime(su, rk, bts, job):
     run = lambda b: rk.end([b], rk.begin([b]))               # noqa: E731
+    reads = [o["reads"] for o in job]
+    expected = lambda bi: su.expected(reads[bi], origin=(job[bi]["key0"], job[bi]["step"]))      # noqa: E731
+    # (the call groups among them: the caller's origin, a frequency table of the batch's own, stat against the reference)
+    consume = lambda b, bi, want: su.consume(b, origin=su.origin(job[bi], np.arange(b.n_reads)), freq=b.gen.new_call_freq(*su.window()), want=want)      # noqa: E731
     b0, b1, b2 = (rk.stage(bt)[0] for bt in bts[:3])
     for name, call in _raw_calls(su, b0).items():           # staged, not run
         assert call() == -4 and name.encode() in b0.gen.L.sqg_last_error(b0.gen.ctx), name
     run(b0); run(b1)
-    want0 = su.expected(reads[0])
-    SC.assert_groups(su.consume(b0), want0, "batch 0")      # (leaves plans of batch 0 in the scratch)
+    want0 = expected(0)
+    SC.assert_groups(consume(b0, 0, want0), want0, "batch 0")      # (leaves plans of batch 0 in the scratch)
     _trimmed_and_pileup(su, b0, reads[0], "batch 0")
     plan0 = b0.chunk_plan(*SC.CHUNK[:2])
     counts = rk.begin([b2])                                 # batch 2 takes the slot of batch 0
@@ -389,10 +479,12 @@ def _lifetime(su, rk, bts, reads):
     np.testing.assert_array_equal(b0.chunk_plan(*SC.CHUNK[:2])[0], plan0[0])
     for name, call in _raw_calls(su, b2).items():           # begun, not ended: refused at once
         assert call() == -4 and name.encode() in err() and b"not been run" in err(), f"{name}: {err()}"
-    SC.assert_groups(su.consume(b1), su.expected(reads[1]), "batch 1 while batch 2 is begun")
+    want1 = expected(1)
+    SC.assert_groups(consume(b1, 1, want1), want1, "batch 1 while batch 2 is begun")
     _trimmed_and_pileup(su, b1, reads[1], "batch 1 while batch 2 is begun")
     rk.end([b2], counts)
-    SC.assert_groups(su.consume(b2), su.expected(reads[2]), "batch 2")
+    want2 = expected(2)
+    SC.assert_groups(consume(b2, 2, want2), want2, "batch 2")
     _trimmed_and_pileup(su, b2, reads[2], "batch 2")        # (the trimmed pileup comes last: the scratch holds batch 2's insert spans ...
     plan2 = b2.site_plan(256, 128, su.focus)[0]             # ... and its site plan at the geometry batch 3 is asked for first)
     b0.free()
@@ -404,11 +496,11 @@ def _lifetime(su, rk, bts, reads):
     assert b3.n_reads == len(bts[3]) == len(bts[2])         # (as many reads: a plan of the freed batch would fit)
     run(b3)
     L, St, _ = SC.CHUNK
-    want3 = su.expected(reads[3])
+    want3 = expected(3)
     np.testing.assert_array_equal(b3.site_plan(256, 128, su.focus)[0], want3["sites 256"]["off"])
     np.testing.assert_array_equal(b3.chunk_plan(L, St, trim=True)[0], want3["chunks f16 medmad"]["off"])
     assert not np.array_equal(want3["sites 256"]["off"], plan2)                                       # (batch 2's plan would show)
-    SC.assert_groups(su.consume(b3), want3, "batch 3")
+    SC.assert_groups(consume(b3, 3, want3), want3, "batch 3")
     _trimmed_and_pileup(su, b3, reads[3], "batch 3")
     for b in (b1, b3):
         b.free()
