@@ -90,7 +90,8 @@ EXPORTS = ("sqg_create", "sqg_destroy", "sqg_last_error", "sqg_strerror", "sqg_d
 DEV_KNOBS = ("SQG_EVENTS_WIDE_MAX", "SQG_TEST_ORDER_FAULT", "SQG_ABL_NOFIX", "SQG_SAMPLER_SERIAL", "SQG_PART_CLAIMS",
              "SQG_TEST_DELTA_X", "SQG_TEST_ROW_TURNS", "SQG_PART_WG_EVENTS", "SQG_SPLIT_CHAINS", "SQG_NO_PART",
              "SQG_PART_SLICE", "SQG_TEST_NO_LEAN", "SQG_STAGE_THREADS", "SQG_NO_PRECOUNT", "SQG_NO_DRAW_AHEAD",
-             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS", "SQG_TEST_SCALE_GRID", "SQG_TEST_CALL_GRID")
+             "SQG_NO_PLACE", "SQG_TEST_B5_MAXBITS", "SQG_TEST_CHUNK_GENERIC", "SQG_TEST_SEG_SPS", "SQG_TEST_SCALE_GRID", "SQG_TEST_CALL_GRID",
+             "SQG_TEST_MAP_TILES")
 
 # include/sqg_chunks.h: bound by load_library only when the library has them (the CPU backend does not)
 EXPORTS_CHUNKS = ("sqg_chunk_plan", "sqg_batch_chunks")
@@ -262,6 +263,35 @@ class CCallStat(C.Structure):
     _fields_ = [("sites", C.c_int64), ("outside", C.c_int64), ("called", C.c_int64), ("agree", C.c_int64)]
 
 
+# include/sqg_map.h: bound the same way; sqg_map_track takes no batch, and its window by value
+EXPORTS_MAP = ("sqg_map_track", "sqg_batch_map")
+MAP_OUTPUTS = ("map_cost", "map_step", "map_key0", "map_key1", "map_cost_other")
+MAP_CFG = ("stay_pen", "skip_pen", "cost_cap", "row_first", "row_count", "strands")
+MAP_DEFAULT = (min(ALIGN_DEFAULT[0], 1 << 17), min(ALIGN_DEFAULT[1], 1 << 17), min(ALIGN_DEFAULT[2], 1 << 17), 0, 256, 3)     # SQG_MAP_DEFAULT
+MAP_NONE = -(1 << 31)                                       # SQG_MAP_NONE
+MAP_MAX_WINDOW, MAP_MAX_ROWS = 1 << 24, 4096
+
+
+class CMapCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in MAP_CFG[:5]] + [("strands", C.c_uint32)]
+
+
+class CMapTrack(C.Structure):
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64), ("fwd", C.c_void_p), ("rev", C.c_void_p)]
+
+
+class CMapOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MAP_OUTPUTS]
+
+
+class MapTrack:
+    """What SignalGenerator.new_map_track() returns and Batch.map() takes: the window [lo, hi) and its levels on either strand, int32 torch
+    tensors [hi - lo] on the context's device (include/sqg_map.h says what they hold); one not asked for is None"""
+
+    def __init__(self, lo, hi, fwd, rev):
+        self.lo, self.hi, self.fwd, self.rev = int(lo), int(hi), fwd, rev
+
+
 # include/sqg_collapse.h: bound the same way
 EXPORTS_COLLAPSE = ("sqg_batch_collapse", "sqg_batch_pileup_rows")
 COLLAPSE_INPUTS = ("ev", "sum", "sumsq", "len")
@@ -322,11 +352,15 @@ _CONSUMER_EXPORTS = (
     (EXPORTS_ALIGN, {"sqg_batch_align": (CAlignCfg, C.c_int64, CAlignIn, CAlignOut)}),
     (EXPORTS_CALL, {"sqg_call_plan": _PLAN,
                     "sqg_batch_call": (CCallCfg, CCallIn, CCallModel, CAlignScale, COrigin, CCallOut, CCallFreq, CCallStat)}),
+    (EXPORTS_MAP, {"sqg_batch_map": (CMapCfg, C.c_int64, CAlignIn, CAlignScale, CMapTrack, CMapOut)}),      # (sqg_map_track: _MAP_TRACK_ARGS)
     (EXPORTS_SCALE, {"sqg_batch_scale": (CScaleCfg, C.c_int64, CScaleIn, CScaleOut),
                      "sqg_batch_align_scaled": (CAlignCfg, C.c_int64, CAlignIn, CAlignScale, CAlignOut)}),
     (EXPORTS_COLLAPSE, {"sqg_batch_collapse": (CCollapseCfg, C.c_int64, CCollapseIn, CCollapseOut),
                         "sqg_batch_pileup_rows": (CPileupCfg, COrigin, C.c_int64, CCollapseIn, CPileupOut, CPileupRowsStat)}),
 )
+
+# sqg_map_track is the one consumer call that takes no batch and two arguments by value: (ctx, lo, hi, levels, fwd, rev), bound on its own
+_MAP_TRACK_ARGS = (C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 
 _ENUMS = {"dtype": {"f16": CHUNK_F16, "f32": CHUNK_F32}, "norm": {"medmad": CHUNK_MEDMAD, "pa": CHUNK_PA},
           "by": {"ref": PILEUP_BY_REF, "kmer": PILEUP_BY_KMER}, "mode": {"moments": SCALE_MOMENTS, "fit": SCALE_FIT},
@@ -476,9 +510,12 @@ def load_library(path: str | None = None):
     L.sqg_build_info.argtypes = []
     for names, table in _CONSUMER_EXPORTS:                  # each header's calls, when the library has them (the CPU backend has none)
         if all(hasattr(L, n) for n in names):
-            for n in names:
+            for n in table:
                 getattr(L, n).restype = C.c_int
                 getattr(L, n).argtypes = [vp, vp] + [C.POINTER(t) for t in table[n]]
+    if hasattr(L, "sqg_map_track"):
+        L.sqg_map_track.restype = C.c_int
+        L.sqg_map_track.argtypes = list(_MAP_TRACK_ARGS)
     _libs[path] = L
     return L
 
@@ -1043,6 +1080,55 @@ class Batch:
         ch.stat = (int(st.sites), int(st.outside), int(st.called), int(st.agree))
         return ch
 
+    def map_shift(self):
+        """(gain, shift): the scale that puts this batch's rows in stored ADC codes on the scale of SignalGenerator.map_levels() -- gain 65536
+        and shift rint(256 * offset[r]) from the offsets the host already has --, int32 tensors [n_reads] on the context's device: what
+        Batch.map(scale=...) takes (include/sqg_map.h; a binding recommendation, not part of the kernel's rule)"""
+        import torch
+        _need(self.gen.L, "sqg_batch_map", "sqg_map.h", "map")
+        if self.res is None:
+            self.wait()
+        dev = torch.device("cuda", self.gen.device)
+        shift = np.clip(np.rint(256.0 * np.asarray(self.offset, np.float64)), -(1 << 26), 1 << 26).astype(np.int32)
+        return torch.full((self.n_reads,), 65536, dtype=torch.int32, device=dev), torch.from_numpy(shift).to(dev)
+
+    def map(self, row_off, sum, len, track, cfg=None, scale=None, outputs=None) -> Chunks:       # noqa: A002  (the header's names)
+        """The first rows of every read -- rows [row_off[r] + row_first, ...) of sum / len, at most row_count of them -- mapped against the
+        level track of a genome window by subsequence DTW in exact integers, on the device (sqg_batch_map, include/sqg_map.h).  row_off, sum
+        and len as in Batch.align().  track: a MapTrack (SignalGenerator.new_map_track(), or synthetic tensors).  cfg: (stay_pen, skip_pen,
+        cost_cap, row_first, row_count, strands), default SQG_MAP_DEFAULT.  scale=(gain, shift) as in Batch.align(); Batch.map_shift() is the
+        one for rows in stored codes against map_levels().  torch tensors [n_reads]: map_cost (int32), map_step (int8: +1 / -1, 0 none),
+        map_key0, map_key1 (int64: the forward coordinate of the k-mer under row 0 / the last row), map_cost_other (int32).  outputs: the
+        names wanted (default all); the others are None."""
+        import torch
+        _need(self.gen.L, "sqg_batch_map", "sqg_map.h", "map")
+        six = MAP_DEFAULT if cfg is None else cfg
+        if isinstance(six, str) or _len(six) != 6:
+            raise SqgError(-1, "map", f"cfg must be ({', '.join(MAP_CFG)}), not {cfg!r}")
+        c = CMapCfg(*(int(v) for v in six[:5]), int(six[5]) & 0xffffffff)
+        want = _want(outputs, MAP_OUTPUTS, "map")
+        off, nr, cin, keep = self._rows("map", row_off, CAlignIn, (sum, len))
+        dev = torch.device("cuda", self.gen.device)
+        if not isinstance(track, MapTrack):
+            raise SqgError(-1, "map", "track must be a MapTrack")
+        w = max(track.hi - track.lo, 0)
+        for name in ("fwd", "rev"):
+            t = getattr(track, name)
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous() and t.numel() >= w):
+                raise SqgError(-1, "map", f"track: {name} must be a contiguous {torch.int32} tensor of at least {w} elements on {dev}")
+        ctr = CMapTrack(track.lo, track.hi, *(None if t is None else t.data_ptr() if t.numel() else keep.data_ptr() for t in (track.fwd, track.rev)))
+        csc = None
+        if scale is not None:
+            if isinstance(scale, torch.Tensor) or _len(scale) != 2:
+                raise SqgError(-1, "map", "scale must be (gain, shift)")
+            for name, t in zip(("gain", "shift"), scale):
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.device == dev and t.is_contiguous() and t.numel() == self.n_reads):
+                    raise SqgError(-1, "map", f"scale: {name} must be a contiguous {torch.int32} tensor of {self.n_reads} elements on {dev}")
+            csc = CAlignScale(*(t.data_ptr() if t.numel() else keep.data_ptr() for t in scale))
+        dts = dict(map_cost=torch.int32, map_step=torch.int8, map_key0=torch.int64, map_key1=torch.int64, map_cost_other=torch.int32)
+        args = (C.byref(c), off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(cin), C.byref(csc) if csc is not None else None, C.byref(ctr))
+        return self._table("sqg_batch_map", args, CMapOut, MAP_OUTPUTS, {n: (self.n_reads, dt) for n, dt in dts.items()}, want, row_off=off)
+
     def _origin(self, who, origin):
         """the C origin of pileup() / pileup_rows() (None: the sampler's) and the arrays it points into"""
         if origin is None:
@@ -1262,6 +1348,43 @@ class SignalGenerator:
             raise SqgError(-1, "call", "hi must not be below lo")
         dev = torch.device("cuda", self.device)
         return CallFreq(lo, int(hi), **{n: (torch.zeros(int(hi) - lo, dtype=torch.int32, device=dev) if n in want else None) for n in CALL_FREQ})
+
+    def map_levels(self):
+        """The recommended levels of include/sqg_map.h from the context's own pore model: int32 [4^k] ([5^k] in an SQG_METH context) on the context's
+        device, rint(256 * level_mean * digitisation / range) in doubles, clipped to +-2^23.  Made once per context; a binding
+        recommendation and not part of the kernel's rule, in the way call_model() is."""
+        import torch
+        _need(self.L, "sqg_map_track", "sqg_map.h", "map")
+        if getattr(self, "_map_levels", None) is None:
+            mean = np.frombuffer(self._model, dtype=np.float32).reshape(-1, 2)[:, 0].astype(np.float64)
+            lv = np.rint(256.0 * mean * np.float64(self.profile.digitisation) / np.float64(self.profile.range))
+            lv = np.nan_to_num(np.clip(lv, -(1 << 23), 1 << 23), nan=0.0).astype(np.int32)
+            self._map_levels = torch.from_numpy(lv).to(torch.device("cuda", self.device))
+        return self._map_levels
+
+    def new_map_track(self, lo: int | None = None, hi: int | None = None, levels=None, fwd: bool = True, rev: bool = True) -> MapTrack:
+        """The level track of the window [lo, hi) of the loaded genome (default: all of it) on both strands (sqg_map_track,
+        include/sqg_map.h): a MapTrack for Batch.map().  levels: int32 [4^k] / [5^k] on the context's device, default map_levels().
+        fwd=False / rev=False leave that strand out (None)."""
+        import torch
+        _need(self.L, "sqg_map_track", "sqg_map.h", "map")
+        lo = 0 if lo is None else int(lo)
+        if hi is None:
+            if getattr(self, "genome_len", None) is None:
+                raise SqgError(-1, "map", "new_map_track without hi= needs a loaded genome")
+            hi = self.genome_len
+        hi = int(hi)
+        dev = torch.device("cuda", self.device)
+        levels = self.map_levels() if levels is None else levels
+        rows = 5 ** self.kmer_size if (self.flags & P.SQ_METH) else 1 << (2 * self.kmer_size)
+        if not (isinstance(levels, torch.Tensor) and levels.dtype == torch.int32 and levels.device == dev and levels.is_contiguous() and levels.numel() >= rows):
+            raise SqgError(-1, "map", f"levels must be a contiguous {torch.int32} tensor of at least {rows} elements on {dev}")
+        w = max(hi - lo, 0) if hi - lo <= MAP_MAX_WINDOW else 0      # (the library refuses the window; nothing is allocated for it)
+        tr = MapTrack(lo, hi, torch.zeros(w, dtype=torch.int32, device=dev) if fwd else None, torch.zeros(w, dtype=torch.int32, device=dev) if rev else None)
+        torch.cuda.synchronize(dev)                         # (the zero fills, before another stream writes the blocks)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None     # noqa: E731
+        self._chk(self.L.sqg_map_track(self.ctx, lo, hi, levels.data_ptr(), ptr(tr.fwd), ptr(tr.rev)), "sqg_map_track")
+        return tr
 
     def call_model(self):
         """(w, c): the recommended model tables of include/sqg_call.h from the context's own pore model, int32 tensors [5^k] on the

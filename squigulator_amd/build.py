@@ -29,10 +29,10 @@ import hashlib
 
 
 def headers() -> list:
-    """every header the one translation unit includes: include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h, include/sqg_collapse.h, include/sqg_scale.h, include/sqg_call.h and all of csrc/*.h (globbed: a new header is a dependency
+    """every header the one translation unit includes: include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h, include/sqg_collapse.h, include/sqg_scale.h, include/sqg_call.h, include/sqg_map.h and all of csrc/*.h (globbed: a new header is a dependency
     the moment it exists)"""
     inc = os.path.join(os.path.dirname(HERE), "include")
-    return [os.path.join(inc, "sqg.h"), os.path.join(inc, "sqg_chunks.h"), os.path.join(inc, "sqg_targets.h"), os.path.join(inc, "sqg_segments.h"), os.path.join(inc, "sqg_sites.h"), os.path.join(inc, "sqg_events.h"), os.path.join(inc, "sqg_pileup.h"), os.path.join(inc, "sqg_detect.h"), os.path.join(inc, "sqg_align.h"), os.path.join(inc, "sqg_collapse.h"), os.path.join(inc, "sqg_scale.h"), os.path.join(inc, "sqg_call.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+    return [os.path.join(inc, "sqg.h"), os.path.join(inc, "sqg_chunks.h"), os.path.join(inc, "sqg_targets.h"), os.path.join(inc, "sqg_segments.h"), os.path.join(inc, "sqg_sites.h"), os.path.join(inc, "sqg_events.h"), os.path.join(inc, "sqg_pileup.h"), os.path.join(inc, "sqg_detect.h"), os.path.join(inc, "sqg_align.h"), os.path.join(inc, "sqg_collapse.h"), os.path.join(inc, "sqg_scale.h"), os.path.join(inc, "sqg_call.h"), os.path.join(inc, "sqg_map.h")] + sorted(glob.glob(os.path.join(CSRC, "*.h")))
 
 
 def source_hash() -> str:

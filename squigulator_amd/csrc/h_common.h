@@ -189,6 +189,14 @@ struct CallScratch {
     void release() { *this = CallScratch(); }
 };
 
+// device scratch of sqg_batch_map (h_map.h): the mapped rows' values and every span's end
+struct MapScratch {
+    DevBuf<long long> d_qoff;                                  // [n_reads+1] first mapped row of every read in d_q
+    DevBuf<int> d_q;                                           // [mapped rows] k_map_rows' q
+    DevBuf<int4> d_rec;                                        // [n_reads][strands][spans] {D, e, S, -} (k_map_dp -> k_map_finish)
+    void release() { *this = MapScratch(); }
+};
+
 struct sqg_ctx {
     HostPool pool_threads;
     struct DrawAhead* draw_ahead = nullptr;        // few workers: their per-read scalar draws, made ahead of staging by a thread of its own (below)
@@ -333,6 +341,7 @@ struct sqg_ctx {
     CollapseScratch collapse;                                  // sqg_batch_collapse, sqg_batch_pileup_rows (h_collapse.h)
     ScaleScratch scale;                                        // sqg_batch_scale (h_scale.h)
     CallScratch call;                                          // sqg_call_plan, sqg_batch_call (h_call.h)
+    MapScratch map;                                            // sqg_batch_map (h_map.h)
     hipStream_t b5_stream = nullptr;                           // the records' upload, framing kernel and copy back: a stream of their own (not behind the next batch's kernels)
     std::string err;
 };

@@ -64,6 +64,7 @@ extern "C" void sqg_destroy(sqg_ctx_t* ctx) {
     ctx->collapse.release();
     ctx->scale.release();
     ctx->call.release();
+    ctx->map.release();
     (void)hipFree(ctx->d_genome); (void)hipFree(ctx->d_contig_off); (void)hipFree(ctx->d_cum); (void)hipFree(ctx->d_nprefix);
     (void)hipFree(ctx->d_trans_csum); (void)hipFree(ctx->d_trans_idx); (void)hipFree(ctx->d_samp);
     (void)hipFree(ctx->d_meth); (void)hipFree(ctx->d_meth_has); (void)hipFree(ctx->d_meth_st);

@@ -86,16 +86,7 @@ __global__ __launch_bounds__(64) void k_align_forward(AlignParams P) {
         const int cnt = (int)min(64LL, m - i0);
         // q of the tile's rows, one per lane, clamped to +-2^26
         int qt = 0;
-        if (lane < cnt) {
-            const long long s = P.sum[R0 + i0 + lane];
-            const long long n = max(P.len[R0 + i0 + lane], 1);
-            const long long p = (long long)((unsigned long long)s << 8);
-            long long q = p / n;
-            if (p % n != 0 && p < 0) q--;                         // floor
-            q = min(max(q, -(1LL << 26)), 1LL << 26);
-            if (SCALED) q = min(max(((gain * q) >> 16) + off, -(1LL << 26)), 1LL << 26);      // (|gain q| <= 2^46; >> of a negative: arithmetic, a floor)
-            qt = (int)q;
-        }
+        if (lane < cnt) qt = rows_q<SCALED>(P.sum[R0 + i0 + lane], P.len[R0 + i0 + lane], gain, off);      // (k_rows.h)
         for (int t = 0; t < cnt; t++) {
             const int i = (int)i0 + t;
             const int q = __builtin_amdgcn_readlane(qt, t);

@@ -1,5 +1,5 @@
 // k_rows.h -- what the kernels that take the caller's rows share (include/sqg_align.h, sqg_collapse.h, sqg_scale.h): the rows as a kernel
-// gets them (RowsIn), the read of a row (rows_read_of) and the wavefront's run combination (wave_runs, wave_run_scan), whose method
+// gets them (RowsIn), a row's value (rows_q), the read of a row (rows_read_of) and the wavefront's run combination (wave_runs, wave_run_scan), whose method
 // k_collapse.h describes.  Part of the device code of the per-read signal path; included through sqg_kernels.h in front of k_align.h.
 #pragma once
 
@@ -8,6 +8,19 @@ struct RowsIn {
     const long long* row_off;                                 // [n_reads+1] device copy of the caller's
     int n_reads; long long n_rows;
 };
+
+// q of a row (include/sqg_scale.h): q0 = floor(256 * sum / max(len, 1)), the product modulo 2^64, clamped to +-2^26; SCALED: ((gain * q0) >> 16) + off,
+// clamped again (gain and off already clamped into their ranges by the caller: |gain q0| <= 2^46; >> of a negative: arithmetic, a floor)
+template <bool SCALED>
+__device__ __forceinline__ int rows_q(const long long s, const int len, const long long gain, const long long off) {
+    const long long n = max(len, 1);
+    const long long p = (long long)((unsigned long long)s << 8);
+    long long q = p / n;
+    if (p % n != 0 && p < 0) q--;                             // floor
+    q = min(max(q, -(1LL << 26)), 1LL << 26);
+    if (SCALED) q = min(max(((gain * q) >> 16) + off, -(1LL << 26)), 1LL << 26);
+    return (int)q;
+}
 
 // the read of row i: the last r in [lo, hi] whose first row, off(r), is <= i (reads without rows are stepped over; off(lo) <= i is given)
 template <class Off>

@@ -1,4 +1,4 @@
-// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h, include/sqg_collapse.h, include/sqg_scale.h and include/sqg_call.h.
+// sqg_hip.hip -- MI355X (gfx950) implementation of include/sqg.h, include/sqg_chunks.h, include/sqg_targets.h, include/sqg_segments.h, include/sqg_sites.h, include/sqg_events.h, include/sqg_pileup.h, include/sqg_detect.h, include/sqg_align.h, include/sqg_collapse.h, include/sqg_scale.h, include/sqg_call.h and include/sqg_map.h.
 //
 // One translation unit: the gfx950 kernels (sqg_kernels.h: k_common.h, k_events.h, k_samples.h, k_sampler.h,
 // k_svb.h) and the host side of the C ABI (h_*.h: context/batch management, staging, launches, results).
@@ -38,6 +38,7 @@
 #include "../../include/sqg_collapse.h"
 #include "../../include/sqg_scale.h"
 #include "../../include/sqg_call.h"
+#include "../../include/sqg_map.h"
 
 #include "sqg_kernels.h"
 
@@ -60,3 +61,4 @@
 #include "h_collapse.h"   // sqg_batch_collapse, sqg_batch_pileup_rows (include/sqg_collapse.h)
 #include "h_scale.h"      // sqg_batch_scale, sqg_batch_align_scaled (include/sqg_scale.h)
 #include "h_call.h"       // sqg_call_plan, sqg_batch_call (include/sqg_call.h)
+#include "h_map.h"        // sqg_map_track, sqg_batch_map (include/sqg_map.h)

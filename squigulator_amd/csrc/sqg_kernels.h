@@ -1,5 +1,5 @@
 // sqg_kernels.h -- gfx950 device code of the per-read signal path (included by sqg_hip.hip); the kernels live in
-// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_rows.h, k_align.h, k_collapse.h, k_scale.h and k_call.h.
+// k_common.h, k_events.h, k_part.h, k_part_events.h, k_samples.h, k_sampler.h, k_svb.h, k_blow5.h, k_chunks.h, k_targets.h, k_segments.h, k_sites.h, k_events_table.h, k_pileup.h, k_detect.h, k_rows.h, k_align.h, k_collapse.h, k_scale.h, k_call.h and k_map.h.
 //
 //   k_init_rows   per-(worker,k-mer) stream seeds                       (src/sim.c:238-257)
 //   k_scan        read lengths -> output offsets
@@ -32,6 +32,9 @@
 //   k_call_*      the CpG sites of every read from 16-byte loads of its bases, ranked by k_chunks.h's scan, then per site the base-5 ranks of its span's
 //                 k-mers under C and under M, the two rows' levels against the caller's event sums in exact integers, the call, and the adds to a
 //                 called frequency per position by no-return integer atomics (include/sqg_call.h)
+//   k_map_*       the genome's expected level track of both strands, then subsequence DTW of every read's first rows against it: a wavefront walks a span of
+//                 1024-position tiles, a strip of 16 positions per lane in registers, the rows as wavefront-uniform values, the path's start carried with
+//                 the cell instead of a traceback; the spans' ends reduced per read in ascending order (include/sqg_map.h)
 //   k_target_*    per-sample targets of those chunks: event starts, clean signal, moves, k-mer rows (include/sqg_targets.h); scan, normalisation and row store are k_chunks.h's
 //
 // Arithmetic modes.  EXACT: every draw goes through the FP64 restatement of nrng()
@@ -66,3 +69,4 @@
 #include "k_collapse.h"
 #include "k_scale.h"
 #include "k_call.h"
+#include "k_map.h"
